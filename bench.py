@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- FASTQ -> SAM throughput of the MI355X-native Kart hot path on synthetic 150 bp paired-end reads.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1 without a launcher: this script starts the N ranks itself -- torch.distributed.run children, before anything
      here touches a GPU -- and relays rank 0's line; under torchrun it is one of the ranks)
 
@@ -256,7 +256,14 @@ def main():
                     help="synthetic genome length; default = hg38-sized (configs[2], the size BASELINE.json's metric is quoted on), "
                          "falling back to configs[1] (4,639,675) if the large index cannot be built on this machine (single rank only)")
     ap.add_argument("--threads", type=int, default=None, help="worker threads per rank (default: the host CPU quota / ranks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's SAM records as DIR/<name>.npy (float64: a fixed, seeded sample of records + whole-output "
+                         "summary, see dump_outputs); pass --pairs as well when two runs must map the same reads (the default job size follows host memory)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)          # (the ranks of N > 1 are started with these arguments)
     args.parts = not args.one_file          # (N > 1) a part per rank unless asked otherwise; `kart-amd -gpu a,b,..` itself defaults to one file
 
     world_env = os.environ.get("WORLD_SIZE")
@@ -660,6 +667,8 @@ def run(args, fallback_note):
                 for blk in iter(lambda: fh.read(1 << 24), b""):
                     h.update(blk)
         line["config"]["sam_sha256_last_step"] = h.hexdigest()
+    if args.dump_outputs and outs:
+        dump_outputs(args.dump_outputs, out_files(outs[-1]), n_reads)
     # the step outputs go first: the side legs below write their own files and must never add to them
     while outs:
         drop(outs.pop(0))
@@ -755,6 +764,75 @@ def run(args, fallback_note):
     if world > 1:
         dist.destroy_process_group()
     return 0
+
+
+DUMP_SAMPLE = 1 << 18         # sampled records: 15 float64 arrays of this length are 31 MB, inside the 64 MB a dump may take
+DUMP_SEED = 950
+DUMP_FIELDS = ("record", "flag", "ref", "pos", "mapq", "cigar_ops", "cigar_ref_len", "cigar_query_len", "mate_ref", "mate_pos", "tlen",
+               "NM", "AS", "XS", "line_crc32")
+
+
+def dump_outputs(dump_dir, sam_files, n_records, chunk=64 << 20):
+    """--dump-outputs: what the last timed step handed its caller -- the SAM text, its files in rank order read as one stream -- as float64
+    arrays DIR/sam_<field>.npy over a fixed, seeded sample of record numbers (the same numbers for the same --pairs): the numeric fields,
+    RNAME / RNEXT as @SQ order (-1 = '*'), the CIGAR's op count and reference / query lengths, the NM / AS / XS tags and the CRC-32 of the
+    whole line (-1 where a field is absent or the stream holds fewer records); sam_summary.npy = [records, header lines, bytes, CRC-32 of
+    the whole stream]."""
+    import re
+    import zlib
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_records, min(n_records, DUMP_SAMPLE), replace=False))
+    cols = {n: np.full(len(pick), -1.0) for n in DUMP_FIELDS}
+    cols["record"][:] = pick
+    refs = {}
+    st = {"lines": 0, "header": 0, "in_header": True, "bytes": 0, "crc": 0}
+
+    def record(i, line):
+        f = line.split(b"\t")
+        ref = refs.get(f[2], -1)
+        ops = re.findall(rb"(\d+)([MIDNSHP=X])", f[5])
+        tags = {t[:2]: t[5:] for t in f[11:]}
+        for n, v in (("flag", int(f[1])), ("ref", ref), ("pos", int(f[3])), ("mapq", int(f[4])), ("cigar_ops", len(ops) if ops else -1),
+                     ("cigar_ref_len", sum(int(k) for k, op in ops if op in b"MDN=X") if ops else -1),
+                     ("cigar_query_len", sum(int(k) for k, op in ops if op in b"MIS=X") if ops else -1),
+                     ("mate_ref", ref if f[6] == b"=" else refs.get(f[6], -1)), ("mate_pos", int(f[7])), ("tlen", int(f[8])),
+                     ("NM", int(tags.get(b"NM", -1))), ("AS", int(tags.get(b"AS", -1))), ("XS", int(tags.get(b"XS", -1))), ("line_crc32", zlib.crc32(line))):
+            cols[n][i] = v
+
+    def lines_of(buf):
+        """the whole lines of buf (every sampled one parsed, the header read); returns the partial line at its end"""
+        ends = np.flatnonzero(np.frombuffer(buf, np.uint8) == 10)
+        starts = np.concatenate(([0], ends[:-1] + 1))
+        k = 0
+        while st["in_header"] and k < len(ends):
+            line = buf[starts[k]:ends[k]]
+            if not line.startswith(b"@"):
+                st["in_header"] = False
+                break
+            if line.startswith(b"@SQ\t"):
+                refs[line.split(b"\t")[1][3:]] = len(refs)
+            st["header"] += 1
+            k += 1
+        first = st["lines"] - st["header"]            # record number of the buffer's first line (after the header)
+        lo, hi = np.searchsorted(pick, [first + k, first + len(ends)])
+        for i in range(lo, hi):
+            j = int(pick[i] - first)
+            record(i, buf[starts[j]:ends[j]])
+        st["lines"] += len(ends)
+        return buf[ends[-1] + 1:] if len(ends) else buf
+
+    carry = b""
+    for path in sam_files:
+        with open(path, "rb") as fh:
+            for blk in iter(lambda: fh.read(chunk), b""):
+                st["crc"] = zlib.crc32(blk, st["crc"])
+                st["bytes"] += len(blk)
+                carry = lines_of(carry + blk)
+    if carry:
+        lines_of(carry + b"\n")
+    os.makedirs(dump_dir, exist_ok=True)
+    for n, a in cols.items():
+        np.save(os.path.join(dump_dir, "sam_%s.npy" % n), a)
+    np.save(os.path.join(dump_dir, "sam_summary.npy"), np.array([st["lines"] - st["header"], st["header"], st["bytes"], st["crc"]], dtype=np.float64))
 
 
 def reference_legs(args, sess, prefix, workdir, f1, f2, n_pairs, threads, cores, want):

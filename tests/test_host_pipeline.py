@@ -8,6 +8,7 @@ import subprocess
 
 import pytest
 
+import ref_runs
 from conftest import GOLDEN, ROOT, SMALL_PREFIX
 
 SAM = os.path.join(GOLDEN, "sam")
@@ -170,10 +171,7 @@ def test_summary_statistics(host_oracle_binary, tmp_path):
 def test_speculative_chunks_match_live_reference(ins_mean, threads, host_oracle_binary, tmp_path):
     """30 chunks mapped concurrently under a speculated EstDistance must commit to exactly the -t 1 output
     (short inserts keep the estimate below MaxInsertSize and moving, so rescue windows and pairing tests
-    depend on it).  Needs the unmodified reference binary (oracle/_ref/kart), i.e. runs where it was built."""
-    ref_bin = os.path.join(ROOT, "oracle", "_ref", "kart")
-    if not os.path.exists(ref_bin):
-        pytest.skip("oracle/_ref/kart not present")
+    depend on it).  Against the unmodified reference's -t 1 (tests/ref_runs.py: live where oracle/_ref/kart was built, else its record)."""
     from kart_amd import synth
     from kart_amd.index_build import read_fasta
     genome = {n: s for n, _, s in read_fasta(os.path.join(GOLDEN, "small.fa"))}
@@ -182,13 +180,11 @@ def test_speculative_chunks_match_live_reference(ins_mean, threads, host_oracle_
     f1, f2 = str(tmp_path / "s_1.fq"), str(tmp_path / "s_2.fq")
     synth.write_fastq(f1, names, r1, mate=1)
     synth.write_fastq(f2, names, r2, mate=2)
-    outs = []
-    for binary, extra in ((ref_bin, ["-t", "1"]), (host_oracle_binary, ["-t", str(threads)])):
-        out = str(tmp_path / (os.path.basename(binary) + ".sam"))
-        subprocess.run([binary, "-silent", "-i", SMALL_PREFIX, "-f", f1, "-f2", f2, "-o", out] + extra, check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        outs.append(open(out, "rb").read())
-    assert outs[0] == outs[1]
+    want = ref_runs.reference("speculative_chunks_%d" % ins_mean, ["-silent", "-i", SMALL_PREFIX, "-f", f1, "-f2", f2, "-t", "1"])
+    out = str(tmp_path / "host.sam")
+    subprocess.run([host_oracle_binary, "-silent", "-i", SMALL_PREFIX, "-f", f1, "-f2", f2, "-o", out, "-t", str(threads)], check=True,
+                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    assert ref_runs.of(open(out, "rb").read()) == want
 
 
 def test_reads_with_dashes_and_ns_match_live_reference(host_oracle_binary, tmp_path):
@@ -196,9 +192,6 @@ def test_reads_with_dashes_and_ns_match_live_reference(host_oracle_binary, tmp_p
     nw_alignment, but AddNewCigarElements / the head and tail trimming (src/tools.cpp:49-104,314-394) scan the gapped strings for
     '-' and take it for a gap column; N runs break the 8-mers.  Short pairs and long reads (-pacbio: host planning, the fragment
     service with and without handed-back jobs, pass 2 from the op strings and from the gapped strings) against kart -t 1."""
-    ref_bin = os.path.join(ROOT, "oracle", "_ref", "kart")
-    if not os.path.exists(ref_bin):
-        pytest.skip("oracle/_ref/kart not present")
     import numpy as np
     from kart_amd import synth
     from kart_amd.index_build import read_fasta
@@ -227,19 +220,19 @@ def test_reads_with_dashes_and_ns_match_live_reference(host_oracle_binary, tmp_p
     fl = str(tmp_path / "d_long.fq")
     synth.write_fastq(fl, lnames, spoil(lreads))
 
-    def run(binary, args, env=None):
+    def run(args, env=None):
         out = str(tmp_path / "o.sam")
-        subprocess.run([binary, "-silent", "-i", SMALL_PREFIX] + args + ["-o", out], check=True, stdout=subprocess.DEVNULL,
+        subprocess.run([host_oracle_binary, "-silent", "-i", SMALL_PREFIX] + args + ["-o", out], check=True, stdout=subprocess.DEVNULL,
                        stderr=subprocess.DEVNULL, env=dict(os.environ, **(env or {})))
-        return open(out, "rb").read()
+        return ref_runs.of(open(out, "rb").read())
 
     short = ["-f", f1, "-f2", f2]
-    assert run(host_oracle_binary, short + ["-t", "3"]) == run(ref_bin, short + ["-t", "1"])
+    assert run(short + ["-t", "3"]) == ref_runs.reference("dashes_and_ns_short", ["-silent", "-i", SMALL_PREFIX] + short + ["-t", "1"])
     long_ = ["-f", fl, "-pacbio"]
-    want = run(ref_bin, long_ + ["-t", "1"])
-    assert want.count(b"\n") > 150
+    want = ref_runs.reference("dashes_and_ns_long", ["-silent", "-i", SMALL_PREFIX] + long_ + ["-t", "1"])
+    assert want["lines"] > 150
     for env in ({}, {"KART_ORACLE_FRAGMENTS": "1"}, {"KART_ORACLE_FRAGMENTS": "3"}, {"KART_ORACLE_FRAGMENTS": "1", "KART_AMD_FINISH_STRINGS": "1"}):
-        assert run(host_oracle_binary, long_ + ["-t", "3"], env) == want, env
+        assert run(long_ + ["-t", "3"], env) == want, env
 
 
 def test_records_cut_short_match_live_reference(host_oracle_binary, tmp_path):
@@ -250,9 +243,6 @@ def test_records_cut_short_match_live_reference(host_oracle_binary, tmp_path):
     reader and the line reader (KART_AMD_NO_MMAP): byte-identical to kart -t 1.  Not compared: a gz mate-1 file cut inside or right
     after a header in paired mode -- the header text becomes a 24-base mate 1, and the reference encodes mate 2 with mate 1's
     length (src/Mapping.cpp:550, SURVEY App. B-5: uninitialised bytes)."""
-    ref_bin = os.path.join(ROOT, "oracle", "_ref", "kart")
-    if not os.path.exists(ref_bin):
-        pytest.skip("oracle/_ref/kart not present")
     raw = [gzip.open(os.path.join(SAM, "pe_%d.fq.gz" % m)).read().split(b"\n")[:2400] for m in (1, 2)]     # 600 records each
     at = 2000                                                                                              # record 500 starts here
 
@@ -262,11 +252,11 @@ def test_records_cut_short_match_live_reference(host_oracle_binary, tmp_path):
         return {"after_header": upto(at + 1), "mid_seq": upto(at + 1, lines[at + 1][:70]), "after_seq": upto(at + 2), "mid_plus": upto(at + 2, b"+"),
                 "after_plus": upto(at + 3), "mid_qual": upto(at + 3, lines[at + 3][:70]), "mid_header": upto(at, lines[at][:5])}
 
-    def run(binary, args, env=None):
+    def run(args, env=None):
         out = str(tmp_path / "o.sam")
-        r = subprocess.run([binary, "-silent", "-i", SMALL_PREFIX] + args + ["-o", out], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
+        r = subprocess.run([host_oracle_binary, "-silent", "-i", SMALL_PREFIX] + args + ["-o", out], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
                            env=dict(os.environ, **(env or {})))
-        return open(out, "rb").read() if r.returncode == 0 else None
+        return ref_runs.of(open(out, "rb").read()) if r.returncode == 0 else None
 
     whole = [b"\n".join(x) + b"\n" for x in raw]
     compared = 0
@@ -281,10 +271,11 @@ def test_records_cut_short_match_live_reference(host_oracle_binary, tmp_path):
                 for args in modes:
                     if gz and which == 0 and len(args) == 4 and name in ("after_header", "mid_header"):
                         continue                                                                           # App. B-5, see above
-                    want = run(ref_bin, args + ["-t", "1"])
-                    assert want is not None
+                    want = ref_runs.reference("records_cut_short_%s_%d_%s_%s" % ("gz" if gz else "plain", which, name, "pe" if len(args) == 4 else "se"),
+                                              ["-silent", "-i", SMALL_PREFIX] + args + ["-t", "1"])
+                    assert want["rc"] == 0
                     for env in ({}, {"KART_AMD_NO_MMAP": "1"}):
-                        assert run(host_oracle_binary, args + ["-t", "3"], env) == want, (gz, which, name, args[:1], env)
+                        assert run(args + ["-t", "3"], env) == want, (gz, which, name, args[:1], env)
                         compared += 1
     assert compared == 80
 
@@ -294,9 +285,6 @@ def test_gz_text_that_gzgets_reads_differently_matches_live_reference(host_oracl
     read without -pacbio, a 1500-character header -- comes back in pieces that are taken for the record's next lines, and an entry
     whose first line does not start with '@' / '>' ends after that line (:162).  The inflated-text parser hands such a window, and
     the rest of the library, to the line reader (gz_text_regular): first batch or late in a paired library, plain gzip or BGZF."""
-    ref_bin = os.path.join(ROOT, "oracle", "_ref", "kart")
-    if not os.path.exists(ref_bin):
-        pytest.skip("oracle/_ref/kart not present")
     from bgzf_util import bgzf
     from kart_amd import synth
     from kart_amd.index_build import read_fasta
@@ -307,40 +295,34 @@ def test_gz_text_that_gzgets_reads_differently_matches_live_reference(host_oracl
         open(path, "wb").write(data)
         return path
 
-    def same(args):
-        outs = []
-        for binary, t in ((ref_bin, "1"), (host_oracle_binary, "4")):
-            out = str(tmp_path / "o.sam")
-            subprocess.run([binary, "-silent", "-i", SMALL_PREFIX] + args + ["-t", t, "-o", out], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-            outs.append(open(out, "rb").read())
-        return outs[0] == outs[1]
+    def same(name, args):
+        out = str(tmp_path / "o.sam")
+        subprocess.run([host_oracle_binary, "-silent", "-i", SMALL_PREFIX] + args + ["-t", "4", "-o", out], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        return ref_runs.of(open(out, "rb").read()) == ref_runs.reference("gzgets_" + name, ["-silent", "-i", SMALL_PREFIX] + args + ["-t", "1"])
 
     names, reads = synth.simulate_long_reads(genome, 40, seed=3, read_len=1200, err=0.02)
     plain = str(tmp_path / "l12.fq")
     synth.write_fastq(plain, names, reads)
-    assert same(["-f", put("l12.fq.gz", gzip.compress(open(plain, "rb").read()))])
+    assert same("long_reads", ["-f", put("l12.fq.gz", gzip.compress(open(plain, "rb").read()))])
     synth.write_fastq(plain, [n + " " + "x" * 1500 for n in names], reads)
-    assert same(["-f", put("lh.fq.gz", gzip.compress(open(plain, "rb").read()))])
+    assert same("long_headers", ["-f", put("lh.fq.gz", gzip.compress(open(plain, "rb").read()))])
     r1 = gzip.open(os.path.join(SAM, "pe_1.fq.gz")).read()
     l2 = gzip.open(os.path.join(SAM, "pe_2.fq.gz")).read().split(b"\n")
     l2[4 * 3000] += b" " + b"y" * 1500                                  # record 3000 of mate file 2: several batches in
     r2 = b"\n".join(l2)
-    assert same(["-f", put("p1.fq.gz", gzip.compress(r1)), "-f2", put("p2.fq.gz", gzip.compress(r2))])
-    assert same(["-f", put("b1.fq.gz", bgzf(r1)), "-f2", put("b2.fq.gz", bgzf(r2, 7000))])
+    assert same("late_long_header_gzip", ["-f", put("p1.fq.gz", gzip.compress(r1)), "-f2", put("p2.fq.gz", gzip.compress(r2))])
+    assert same("late_long_header_bgzf", ["-f", put("b1.fq.gz", bgzf(r1)), "-f2", put("b2.fq.gz", bgzf(r2, 7000))])
     l1 = r1.split(b"\n")
     l1[4 * 1000] = b"X" + l1[4 * 1000][1:]
     nh = put("nh.fq.gz", gzip.compress(b"\n".join(l1)))
-    assert same(["-f", nh])
-    assert same(["-f", nh, "-f2", put("q2.fq.gz", gzip.compress(gzip.open(os.path.join(SAM, "pe_2.fq.gz")).read()))])
+    assert same("no_at_single", ["-f", nh])
+    assert same("no_at_paired", ["-f", nh, "-f2", put("q2.fq.gz", gzip.compress(gzip.open(os.path.join(SAM, "pe_2.fq.gz")).read()))])
 
 
 def test_pacbio_with_mate_files_matches_live_reference(host_oracle_binary, tmp_path):
     """-pacbio with -f / -f2 (or -p): the reference maps the reads one by one (src/Mapping.cpp:514-529) but prints an even-sized
     chunk through OutputPairedAlignments (:598) -- mate 2 is held reverse-complemented and shown flipped back by a forward report.
     Mate files of 61 reads (the last chunk is odd: printed singly), an unmappable read in either file, gz, -p, -m."""
-    ref_bin = os.path.join(ROOT, "oracle", "_ref", "kart")
-    if not os.path.exists(ref_bin):
-        pytest.skip("oracle/_ref/kart not present")
     import numpy as np
     from kart_amd import synth
     from kart_amd.index_build import read_fasta
@@ -358,16 +340,18 @@ def test_pacbio_with_mate_files_matches_live_reference(host_oracle_binary, tmp_p
     for src, dst in ((f1, g1), (f2, g2)):
         open(dst, "wb").write(gzip.compress(open(src, "rb").read()))
 
-    def run(binary, args, env=None):
+    def run(args, env=None):
         out = str(tmp_path / "o.sam")
-        subprocess.run([binary, "-silent", "-i", SMALL_PREFIX] + args + ["-o", out], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
+        subprocess.run([host_oracle_binary, "-silent", "-i", SMALL_PREFIX] + args + ["-o", out], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
                        env=dict(os.environ, **(env or {})))
-        return open(out, "rb").read()
+        return ref_runs.of(open(out, "rb").read())
 
-    for args in (["-f", f1, "-f2", f2, "-pacbio"], ["-f", g1, "-f2", g2, "-pacbio"], ["-f", fi, "-p", "-pacbio"], ["-f", f1, "-f2", f2, "-pacbio", "-m"]):
-        want = run(ref_bin, args + ["-t", "1"])
+    for name, args in (("mates", ["-f", f1, "-f2", f2, "-pacbio"]), ("mates_gz", ["-f", g1, "-f2", g2, "-pacbio"]), ("interleaved", ["-f", fi, "-p", "-pacbio"]),
+                       ("mates_multi_hit", ["-f", f1, "-f2", f2, "-pacbio", "-m"])):
+        want = ref_runs.reference("pacbio_" + name, ["-silent", "-i", SMALL_PREFIX] + args + ["-t", "1"])
+        assert want["rc"] == 0
         for env in ({}, {"KART_ORACLE_FRAGMENTS": "1"}):
-            assert run(host_oracle_binary, args + ["-t", "4"], env) == want, (args, env)
+            assert run(args + ["-t", "4"], env) == want, (args, env)
 
 
 def test_bgzf_inputs_are_inflated_member_by_member(host_oracle_binary, tmp_path):
@@ -411,9 +395,6 @@ def test_damaged_gz_input_yields_what_the_reference_still_reads(host_oracle_bina
     maps it; one large gzread() fails as a whole (rounds 2-3 lost the batch: here the whole library).  GzText::replay() reads the
     file again the way gzgets() does.  Same records as kart -t 1 -- except the one the damage cuts in two, for whose missing lines
     the reference prints stale contents of its line buffer (src/GetData.cpp:160-175)."""
-    ref_bin = os.path.join(ROOT, "oracle", "_ref", "kart")
-    if not os.path.exists(ref_bin):
-        pytest.skip("oracle/_ref/kart not present")
     from bgzf_util import bgzf
     r1 = gzip.open(os.path.join(SAM, "pe_1.fq.gz")).read()
     r2 = gzip.open(os.path.join(SAM, "pe_2.fq.gz")).read()
@@ -424,17 +405,17 @@ def test_damaged_gz_input_yields_what_the_reference_still_reads(host_oracle_bina
         d[len(d) // 2] ^= 0x55
         bad1 = str(tmp_path / (name + "_1.fq.gz"))
         open(bad1, "wb").write(bytes(d))
-        outs = []
-        for binary, t in ((ref_bin, "1"), (host_oracle_binary, "8")):
-            out = str(tmp_path / "o.sam")
-            r = subprocess.run([binary, "-silent", "-i", SMALL_PREFIX, "-f", bad1, "-f2", good2, "-t", t, "-o", out],
-                               stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-            assert r.returncode == 0 or binary == ref_bin         # (where the damage leaves it a negative length the reference aborts)
-            outs.append(open(out, "rb").read().split(b"\n") if r.returncode == 0 else None)
-        ref, got = outs
+        # (where the damage leaves it a negative length the reference aborts)
+        want = ref_runs.reference("damaged_gz_" + name, ["-silent", "-i", SMALL_PREFIX, "-f", bad1, "-f2", good2, "-t", "1"], lines=True)
+        out = str(tmp_path / "o.sam")
+        r = subprocess.run([host_oracle_binary, "-silent", "-i", SMALL_PREFIX, "-f", bad1, "-f2", good2, "-t", "8", "-o", out],
+                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        assert r.returncode == 0
+        got = ref_runs.line_crcs(ref_runs.of(open(out, "rb").read(), lines=True))
         assert len(got) > 1000, (name, len(got))                   # the reads before the damage are mapped
-        if ref is None:
+        if want["rc"] != 0:
             continue
+        ref = ref_runs.line_crcs(want)
         assert len(got) == len(ref), (name, len(got), len(ref))
         differing = [i for i, (x, y) in enumerate(zip(ref, got)) if x != y]
         assert len(differing) <= 1 and all(i >= len(ref) - 4 for i in differing), (name, differing[:5])
@@ -443,10 +424,7 @@ def test_damaged_gz_input_yields_what_the_reference_still_reads(host_oracle_bina
 def test_odd_input_files_match_live_reference(host_oracle_binary, tmp_path):
     """inputs the readers must treat exactly like the reference's getline()/gzgets() loops: a second file shorter than the
     first, CRLF line ends, no newline at the end of the file, empty files, an interleaved file with an odd number of records,
-    one gz and one plain mate file.  Needs oracle/_ref/kart (live comparison)."""
-    ref_bin = os.path.join(ROOT, "oracle", "_ref", "kart")
-    if not os.path.exists(ref_bin):
-        pytest.skip("oracle/_ref/kart not present")
+    one gz and one plain mate file.  Against the reference's -t 1 (tests/ref_runs.py)."""
     src1 = open(materialise(str(tmp_path), "pe_1.fq"), "rb").read().split(b"\n")
     src2 = open(materialise(str(tmp_path), "pe_2.fq"), "rb").read().split(b"\n")
 
@@ -494,12 +472,10 @@ def test_odd_input_files_match_live_reference(host_oracle_binary, tmp_path):
         "fasta_and_fastq": ["-f", fasta("m1.fa", src1, 2000), "-f2", a2],
     })
     for name, args in cases.items():
-        outs = []
-        for binary, extra in ((ref_bin, ["-t", "1"]), (host_oracle_binary, ["-t", "4"])):
-            out = str(tmp_path / (name + "_" + os.path.basename(binary) + ".sam"))
-            r = subprocess.run([binary, "-silent", "-i", SMALL_PREFIX] + args + ["-o", out] + extra, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=300)
-            outs.append((r.returncode, open(out, "rb").read()))
-        assert outs[0] == outs[1], name
+        want = ref_runs.reference("odd_input_" + name, ["-silent", "-i", SMALL_PREFIX] + args + ["-t", "1"])
+        out = str(tmp_path / (name + ".sam"))
+        r = subprocess.run([host_oracle_binary, "-silent", "-i", SMALL_PREFIX] + args + ["-o", out, "-t", "4"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=300)
+        assert ref_runs.digest(r.returncode, open(out, "rb").read()) == want, name
 
 
 @pytest.mark.parametrize("threads", [1, 3, 16])
@@ -581,10 +557,9 @@ def test_output_to_a_pipe(host_oracle_binary, tmp_path):
 def test_multi_hit_flags_match_live_reference_where_assigned(host_oracle_binary, tmp_path):
     """-m paired-end: the reference prints an uninitialised SamFlag for some secondary records.
     The pipeline marks exactly those with KART_AMD_UNSET_FLAG; every other FLAG -- and every other column of every
-    record -- must equal the live reference's."""
-    ref_bin = os.path.join(ROOT, "oracle", "_ref", "kart")
-    if not os.path.exists(ref_bin):
-        pytest.skip("oracle/_ref/kart not present on this machine")
+    record -- must equal the reference's (reference_sam_and_never_assigned_flags and assert_sam_equals_reference_with_its_own_mask on
+    the lines' digests, tests/ref_runs.py)."""
+    import numpy as np
     from kart_amd import synth
     from kart_amd.index_build import read_fasta
     genome = {n: s for n, _, s in read_fasta(os.path.join(GOLDEN, "small.fa"))}
@@ -592,8 +567,21 @@ def test_multi_hit_flags_match_live_reference_where_assigned(host_oracle_binary,
     f1, f2 = str(tmp_path / "a_1.fq"), str(tmp_path / "a_2.fq")
     synth.write_fastq(f1, names, r1, mate=1)
     synth.write_fastq(f2, names, r2, mate=2)
-    ref_lines, never = reference_sam_and_never_assigned_flags(ref_bin, ["-i", SMALL_PREFIX, "-f", f1, "-f2", f2, "-m"], str(tmp_path))
+    runs = [ref_runs.reference("multi_hit_perturb_%d" % p, ["-silent", "-t", "1", "-i", SMALL_PREFIX, "-f", f1, "-f2", f2, "-m"],
+                               env={"MALLOC_PERTURB_": str(p), "GLIBC_TUNABLES": "glibc.malloc.tcache_count=0"}, lines=True) for p in (85, 170)]
+    assert [r["rc"] for r in runs] == [0, 0]
+    a, b = (ref_runs.line_crcs(r) for r in runs)
+    a_nf, b_nf = (ref_runs.line_crcs(r, "line_crc_without_flag") for r in runs)
+    assert len(a) == len(b) and (a_nf == b_nf).all()                    # only the FLAG may depend on the heap
+    never = set(np.flatnonzero(a != b).tolist())
     out = str(tmp_path / "host.sam")
     subprocess.run([host_oracle_binary, "-silent", "-i", SMALL_PREFIX, "-f", f1, "-f2", f2, "-m", "-o", out, "-t", "4"], check=True,
                    stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, env=dict(os.environ, KART_AMD_UNSET_FLAG=str(UNSET_FLAG)))
-    assert_sam_equals_reference_with_its_own_mask(ref_lines, never, open(out, "rb").read())
+    text = open(out, "rb").read()
+    g = ref_runs.of(text, lines=True)
+    g_full, g_nf = ref_runs.line_crcs(g), ref_runs.line_crcs(g, "line_crc_without_flag")
+    assert len(g_full) == len(a)
+    sentinel = {i for i, y in enumerate(text.split(b"\n")) if not y.startswith(b"@") and y.split(b"\t")[1:2] == [str(UNSET_FLAG).encode()]}
+    for i in range(len(a)):
+        assert g_nf[i] == a_nf[i] if i in sentinel else (g_full[i] == a[i] or i in never), i
+    assert sentinel == never, (sorted(sentinel ^ never)[:10], len(sentinel), len(never))

@@ -8,7 +8,8 @@ import subprocess
 
 import pytest
 
-from conftest import GOLDEN, ROOT, SMALL_PREFIX
+import ref_runs
+from conftest import GOLDEN, SMALL_PREFIX
 from test_host_pipeline import CASES, host_oracle_binary, materialise, run_case   # noqa: F401  (fixture)
 
 
@@ -26,10 +27,8 @@ def test_sharded_golden(case, devices, host_oracle_binary, tmp_path):
 @pytest.fixture(scope="module")
 def moving_estimate_input(tmp_path_factory):
     """40 chunks whose insert sizes drift (300 -> 180): the estimate keeps moving below MaxInsertSize, so rescue windows and
-    pairing tests depend on the totals in front of every chunk -- the case the settle step of a later shard exists for"""
-    ref_bin = os.path.join(ROOT, "oracle", "_ref", "kart")
-    if not os.path.exists(ref_bin):
-        pytest.skip("oracle/_ref/kart not present")
+    pairing tests depend on the totals in front of every chunk -- the case the settle step of a later shard exists for; with the
+    reference's -t 1 SAM of them (tests/ref_runs.py)"""
     from kart_amd import synth
     from kart_amd.index_build import read_fasta
     tmp = tmp_path_factory.mktemp("moving")
@@ -44,9 +43,9 @@ def moving_estimate_input(tmp_path_factory):
             synth.write_fastq(p2, names, r2, mate=2)
             o1.write(open(p1, "rb").read())
             o2.write(open(p2, "rb").read())
-    ref = str(tmp / "ref.sam")
-    subprocess.run([ref_bin, "-silent", "-i", SMALL_PREFIX, "-f", f1, "-f2", f2, "-o", ref, "-t", "1"], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return f1, f2, open(ref, "rb").read()
+    ref = ref_runs.reference("moving_estimate", ["-silent", "-i", SMALL_PREFIX, "-f", f1, "-f2", f2, "-t", "1"])
+    assert ref["rc"] == 0
+    return f1, f2, ref
 
 
 @pytest.mark.parametrize("devices", ["0", "0,1", "0,1,2", "0,1,2,3,4,5,6,7"])
@@ -56,7 +55,7 @@ def test_sharded_moving_estimate_matches_live_reference(devices, moving_estimate
     r = subprocess.run([host_oracle_binary, "-silent", "-i", SMALL_PREFIX, "-f", f1, "-f2", f2, "-o", out, "-gpu", devices, "-t", "8"],
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=dict(os.environ, KART_AMD_VERBOSE="1"))
     assert r.returncode == 0, r.stdout.decode()[-600:]
-    assert open(out, "rb").read() == ref
+    assert ref_runs.of(open(out, "rb").read()) == ref
     assert "All the 160000 paired-end reads" in r.stdout.decode()
 
 
@@ -97,7 +96,7 @@ def test_sharded_parts_written_while_mapping_match_live_reference(devices, movin
         r = subprocess.run([host_oracle_binary, "-silent", "-i", SMALL_PREFIX, "-f", f1, "-f2", f2, "-o", out, "-gpu", devices, "-parts", "-t", "8"],
                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=dict(os.environ, KART_AMD_VERBOSE="1", **env))
         assert r.returncode == 0, r.stdout.decode()[-600:]
-        assert b"".join(open("%s.%d" % (out, q), "rb").read() for q in range(n)) == ref, env
+        assert ref_runs.of(b"".join(open("%s.%d" % (out, q), "rb").read() for q in range(n))) == ref, env
         if not env:
             for l in r.stdout.decode().splitlines():
                 if l.startswith("shard ") and "chunks of text written again" in l:
