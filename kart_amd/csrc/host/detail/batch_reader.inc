@@ -7,6 +7,7 @@ struct RunTotals {
 	double t_read = 0, t_encode = 0, t_seed = 0, t_a = 0, t_nw = 0, t_c = 0, t_commit = 0, t_drain = 0, t_lib = 0, t_format = 0;   // KART_AMD_VERBOSE stage timers
 	double t_long_wait = 0;                           // long reads: the main loop waiting for a batch's device report
 	double t_shard_wait = 0, t_shard_settle = 0;     // a deferred shard: waiting for the totals of the shard before it, settling its own chunks against them
+	WriterTimes writer;                               // where the writer drain (t_drain) went, and the windows unmapped during the run
 };
 
 struct Batch {

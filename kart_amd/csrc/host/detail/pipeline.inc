@@ -2,6 +2,15 @@
 // or the device stream's lanes, the in-order commit with the EstDistance replay, the long-read overlap, a shard's settling -- and plan_shard().
 // The pieces it is made of: chunk_state.inc (ChunkState, Pool), writer.inc, chunk_stages.inc, batch_reader.inc, deferred.inc, stream.inc.
 // A fragment of mapper.cpp (included there, inside namespace kart { namespace { ... } }); not a translation unit of its own.
+// the Writer's last items, the windows still mapped and the exact size; the parts of its time go to the verbose line
+void finish_writer(Writer &w, RunTotals &tot)
+{
+	w.finish();
+	const WriterTimes &t = w.times();
+	tot.writer.wait += t.wait; tot.writer.unmap += t.unmap; tot.writer.truncate += t.truncate;
+	tot.writer.unmap_beside += t.unmap_beside; tot.writer.windows_beside += t.windows_beside; tot.writer.windows_at_end += t.windows_at_end;
+}
+
 void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Shard &shard, FILE *&shard_out)
 {
 	const int chunk_limit = cx.opt.pacbio ? 10 : 4000;   // ReadChunkSize, src/structure.h:21; src/GetData.cpp:140
@@ -355,7 +364,7 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 		// settle: the true totals in front of this shard, then the same fixed-point rounds as the in-process commit
 		Rendezvous *rv = shard.rdv;
 		const double t_mapped = now_s();
-		if (eager) writer->finish();                 // (everything mapped so far is in the file: settling may replace a chunk's text)
+		if (eager) finish_writer(*writer, tot);     // (everything mapped so far is in the file: settling may replace a chunk's text)
 		shard.wait([&]() { return rv->done[shard.rank - 1].load() != 0; }, "waiting for the previous shard");
 		tot.t_shard_wait = now_s() - t_mapped;
 		const double t_settle = now_s();
@@ -430,7 +439,7 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 		}
 	}
 	double td = now_s();
-	if (writer) writer->finish();
+	if (writer) finish_writer(*writer, tot);
 	tot.t_drain += now_s() - td;
 	if (shard.active()) shard.rdv->written[shard.rank].store(1);
 }

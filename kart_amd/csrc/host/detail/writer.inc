@@ -188,13 +188,29 @@ int64_t host_memory_available()
 	return best;
 }
 
+// the output window in bytes: KART_AMD_OUT_WINDOW_MB (default 1024), a whole number of pages
+size_t out_window_bytes()
+{
+	const char *env = getenv("KART_AMD_OUT_WINDOW_MB");
+	const long long mb = env ? std::max(1LL, atoll(env)) : 1024;
+	return (size_t)mb << 20;
+}
+
+// where the time of Writer::finish() went (KART_AMD_VERBOSE), and the windows unmapped while the run went on
+struct WriterTimes {
+	double wait = 0, unmap = 0, truncate = 0;        // finish(): the queue running dry, the windows still mapped, the exact size
+	double unmap_beside = 0;                         // the unmapping thread's munmap calls during the run
+	int64_t windows_beside = 0, windows_at_end = 0;
+};
+
 class Writer {
 public:
 	// last_writer: this process writes the end of the file (a shard in front of others must neither shrink the file nor set its size)
-	explicit Writer(FILE *out, int n_threads = 4, bool last_writer = true) : fd_(fileno(out)), last_writer_(last_writer)
+	explicit Writer(FILE *out, int n_threads = 4, bool last_writer = true) : fd_(fileno(out)), last_writer_(last_writer), win_size_(out_window_bytes())
 	{
 		fflush(out);
 		off_ = lseek(fd_, 0, SEEK_CUR);
+		first_off_ = off_;
 		seekable_ = off_ >= 0;
 		if (seekable_) {
 			struct stat sb;
@@ -217,6 +233,15 @@ public:
 		// page cache's own lock.  Measured at 100 M reads per step, alternating on one box (profiles/r04za_ab_pwrite.log, r04zb):
 		// 6 + 0 threads 30.5 / 32.5 M mapped reads/s, 6 + 1 34.4 / 33.5, 7 + 1 34.1 / 36.7, 8 + 1 35.1 / 35.9, 6 + 2 33.9 / 35.3, 7 + 2 32.6 / 34.7.
 		const int n_pwrite = !(seekable_ && use_map_) ? 0 : getenv("KART_AMD_PWRITE_THREADS") ? std::max(0, atoi(getenv("KART_AMD_PWRITE_THREADS"))) : (n_threads >= 4 ? 1 : 0);
+		// A window whose bytes are all in the file is unmapped while the run goes on, by a thread of its own: kept until finish(),
+		// 39 GB of windows (9.5 M page-table entries of shmem pages) were torn down on one thread after the last byte, inside the run.
+		mode_ = getenv("KART_AMD_WRITER_MODE") ? atoi(getenv("KART_AMD_WRITER_MODE")) : 1;
+		release_ = use_map_ && (mode_ == 1 || mode_ == 2);
+		if (release_) {
+			const char *where = getenv("KART_AMD_UNMAP_CPUS");
+			const bool on_lanes = where && !strcmp(where, "lanes");
+			unmap_th_ = std::thread([this, on_lanes]() { if (on_lanes) pin_lane_thread(); else pin_io_thread(); unmap_loop(); });
+		}
 		for (int t = 0; t < n_threads; ++t) th_.emplace_back([this]() { pin_io_thread(); loop(false); });
 		for (int t = 0; t < n_pwrite; ++t) th_.emplace_back([this]() { pin_io_thread(); loop(true); });
 	}
@@ -267,39 +292,12 @@ public:
 		q_.push_back(std::move(it));
 		cv_.notify_one();
 	}
-	// room for n bytes at the end of what has been handed out; the caller fills it through map_range() / write_at()
-	bool mapped() const { return use_map_; }
-	off_t reserve(size_t n)
-	{
-		std::lock_guard<std::mutex> lk(mu_);
-		off_t at = off_;
-		off_ += (off_t)n;
-		grow_locked();
-		ask_ahead();
-		return at;
-	}
-	char *map_range(off_t at, size_t n)               // null when the range straddles two windows
-	{
-		off_t wi = at / (off_t)kWindow;
-		size_t in = (size_t)(at - wi * (off_t)kWindow);
-		if (in + n > kWindow) return nullptr;
-		char *w = window(wi);
-		return w ? w + in : nullptr;
-	}
-	void write_at(off_t at, const char *p, size_t left)
-	{
-		while (left > 0) {
-			off_t wi = at / (off_t)kWindow;
-			char *w = window(wi);
-			if (!w) { run_fail("mmap of the output file: %s", strerror(errno)); discard_ = true; return; }
-			size_t in = (size_t)(at - wi * (off_t)kWindow), n = std::min(left, kWindow - in);
-			memcpy(w + in, p, n);
-			p += n; left -= n; at += (off_t)n;
-		}
-	}
+	// Every window is unmapped before this returns: the ones released during the run by the unmapping thread (joined here, after
+	// whatever it still had in hand) and the ones still open -- normally the last one or two.
 	void finish()
 	{
 		if (th_.empty()) return;
+		const double t0 = now_s();
 		{
 			std::lock_guard<std::mutex> lk(mu_);
 			stop_ = true;
@@ -317,19 +315,33 @@ public:
 			extended_ = extended_ || alloc_end_ > alloc_from_;
 		}
 		if (turn_ && have_turn_) { have_turn_ = false; turn_->store(0); }          // (never keep the turn past the last item)
-		for (const std::pair<const off_t, char *> &w : win_) { SigbusGuard::remove(w.second); munmap(w.second, kWindow); }
+		const double t1 = now_s();
+		if (unmap_th_.joinable()) {
+			{
+				std::lock_guard<std::mutex> lk(umu_);
+				unmap_stop_ = true;
+			}
+			ucv_.notify_all();
+			unmap_th_.join();
+		}
+		for (const std::pair<const off_t, char *> &w : win_) { SigbusGuard::remove(w.second); munmap(w.second, win_size_); times_.windows_at_end++; }
 		win_.clear();
+		done_.clear();
 		if (guarded_) { SigbusGuard::release(); guarded_ = false; }
+		const double t2 = now_s();
 		if (seekable_) {
 			if ((use_map_ || extended_) && last_writer_ && ftruncate(fd_, off_) != 0) run_fail("ftruncate of the output file: %s", strerror(errno));    // the exact size
 			lseek(fd_, off_, SEEK_SET);
 		}
+		const double t3 = now_s();
+		times_.wait += t1 - t0; times_.unmap += t2 - t1; times_.truncate += t3 - t2;
 	}
+	const WriterTimes &times() const { return times_; }
 
 private:
-	// windows of the output file mapped shared, kept until the end: unmapping per chunk costs a TLB shoot-down across all the
-	// threads of the process every time
-	static constexpr size_t kWindow = (size_t)1 << 30, kGrow = (size_t)256 << 20, kAhead = (size_t)768 << 20, kAllocStep = (size_t)64 << 20;
+	// windows of the output file mapped shared, each kept until every byte of it this Writer hands out has been copied: unmapping per
+	// chunk costs a TLB shoot-down across all the threads of the process every time
+	static constexpr size_t kGrow = (size_t)256 << 20, kAhead = (size_t)768 << 20, kAllocStep = (size_t)64 << 20;
 	struct Item {
 		std::string text;
 		off_t off;
@@ -467,11 +479,54 @@ private:
 		std::lock_guard<std::mutex> lk(win_mu_);
 		std::map<off_t, char *>::iterator it = win_.find(index);
 		if (it != win_.end()) return it->second;
-		void *m = mmap(nullptr, kWindow, PROT_READ | PROT_WRITE, MAP_SHARED, fd_, index * (off_t)kWindow);
+		void *m = mmap(nullptr, win_size_, PROT_READ | PROT_WRITE, MAP_SHARED, fd_, index * (off_t)win_size_);
 		if (m == MAP_FAILED) return nullptr;
 		win_[index] = (char *)m;
-		if (guarded_) SigbusGuard::add(m, kWindow);
+		if (guarded_) SigbusGuard::add(m, win_size_);
 		return (char *)m;
+	}
+	// the item at [at, at + n) has been handled (copied, written, or dropped after a failure), by whichever path: each window it
+	// covers counts its bytes, and a window that holds all it will ever get from this Writer -- its bytes from first_off_ on, which
+	// are handed out in order, so the queue has passed its end -- goes to the unmapping thread.  Nothing is mapped there again.
+	void complete(off_t at, size_t n)
+	{
+		if (!release_ || n == 0) return;
+		const off_t W = (off_t)win_size_, end = at + (off_t)n;
+		std::lock_guard<std::mutex> lk(win_mu_);
+		while (at < end) {
+			const off_t wi = at / W, w_end = (wi + 1) * W, upto = std::min(end, w_end);
+			off_t &d = done_[wi];
+			d += upto - at;
+			at = upto;
+			if (d < w_end - std::max(wi * W, first_off_)) continue;
+			done_.erase(wi);
+			std::map<off_t, char *>::iterator it = win_.find(wi);
+			if (it == win_.end()) continue;                  // (none of it went through the mapping)
+			{
+				std::lock_guard<std::mutex> ul(umu_);
+				retired_.push_back(it->second);
+			}
+			ucv_.notify_one();
+			win_.erase(it);
+		}
+	}
+	void unmap_loop()
+	{
+		std::unique_lock<std::mutex> lk(umu_);
+		for (;;) {
+			ucv_.wait(lk, [this]() { return unmap_stop_ || !retired_.empty(); });
+			if (retired_.empty()) return;
+			char *w = retired_.front();
+			retired_.pop_front();
+			lk.unlock();
+			const double t0 = now_s();
+			SigbusGuard::remove(w);
+			munmap(w, win_size_);
+			const double dt = now_s() - t0;
+			lk.lock();
+			times_.unmap_beside += dt;
+			times_.windows_beside++;
+		}
 	}
 	void loop(bool by_pwrite)
 	{
@@ -487,11 +542,9 @@ private:
 			off_t at = it.off;
 			size_t hold_at = 0;
 			if (by_pwrite) it.map = false;
-			if (it.map) {
-				size_t bytes = it.text.size();
-				if (!it.pieces.empty()) { bytes = 0; for (const TextPiece &tp : it.pieces) bytes += tp.n; }
-				wait_allocated(it.off + (off_t)bytes);
-			}
+			size_t bytes = it.text.size();
+			if (!it.pieces.empty()) { bytes = 0; for (const TextPiece &tp : it.pieces) bytes += tp.n; }
+			if (it.map) wait_allocated(it.off + (off_t)bytes);
 			turn_acquire();
 			const size_t n_parts = it.pieces.empty() ? 1 : it.pieces.size();
 			for (size_t part = 0; part < n_parts && !discard_; ++part) {
@@ -504,7 +557,9 @@ private:
 				else { p = it.text.data() + hold_at; hold_at += tp.n; }
 			}
 			while (it.map && left > 0) {
-				static const int mode = getenv("KART_AMD_WRITER_MODE") ? atoi(getenv("KART_AMD_WRITER_MODE")) : 1;   // experiment switch: 0 a mapping per chunk (1.60-1.65 s per 20 M reads), 1 persistent windows (1.35-1.9 s), 2 windows + MADV_POPULATE_WRITE (2.2-2.3 s); pwrite: 3.4 s
+				// experiment switch (mode_): 0 a mapping per chunk (1.60-1.65 s per 20 M reads), 1 windows (1.35-1.9 s), 2 windows + MADV_POPULATE_WRITE
+				// (2.2-2.3 s), 3 windows kept until finish() (the form before they were released during the run); pwrite: 3.4 s
+				const int mode = mode_;
 				if (mode == 0) {
 					static const size_t page = (size_t)sysconf(_SC_PAGESIZE);
 					off_t base = at - (off_t)((size_t)at % page);
@@ -516,13 +571,13 @@ private:
 					p += left; at += (off_t)left; left = 0;
 					break;
 				}
-				off_t wi = at / (off_t)kWindow;
+				off_t wi = at / (off_t)win_size_;
 				char *w = window(wi);
 				if (!w) break;
-				size_t in = (size_t)(at - wi * (off_t)kWindow), n = std::min(left, kWindow - in);
+				size_t in = (size_t)(at - wi * (off_t)win_size_), n = std::min(left, win_size_ - in);
 #ifdef MADV_POPULATE_WRITE
 				if (mode == 2) {	// the pages of the range in one call instead of one write fault per 4 KB page
-					size_t a = in & ~(size_t)4095, b = std::min(kWindow, (in + n + 4095) & ~(size_t)4095);
+					size_t a = in & ~(size_t)4095, b = std::min(win_size_, (in + n + 4095) & ~(size_t)4095);
 					madvise(w + a, b - a, MADV_POPULATE_WRITE);
 				}
 #endif
@@ -536,6 +591,7 @@ private:
 			}
 			}
 			turn_release();
+			if (seekable_) complete(it.off, bytes);
 			if (it.pending) {
 				std::lock_guard<std::mutex> lk(*it.done_mu);
 				it.pending->fetch_sub(1);
@@ -565,6 +621,18 @@ private:
 	bool alloc_stop_ = false;
 	std::mutex mu_, win_mu_;
 	std::map<off_t, char *> win_;
+	// releasing the windows during the run (complete(), unmap_loop())
+	const size_t win_size_;
+	int mode_ = 1;
+	bool release_ = false;
+	off_t first_off_ = 0;                          // where this Writer's text starts (a shard's part, a rewritten tail: inside a window)
+	std::map<off_t, off_t> done_;                  // window -> its bytes copied so far (win_mu_)
+	std::thread unmap_th_;
+	std::mutex umu_;
+	std::condition_variable ucv_;
+	std::deque<char *> retired_;
+	bool unmap_stop_ = false;
+	WriterTimes times_;
 	std::condition_variable cv_;
 	std::deque<Item> q_;
 	bool stop_ = false;
