@@ -321,7 +321,7 @@ int  kg_nw_batch_device(kg_index *ix, const char *d_frag1, const int64_t *d_off1
 int  kg_fragments_batch(kg_index *ix, const char *frag1, const int64_t *off1, const int64_t *gpos, const int32_t *glen, int64_t n,
                         int pacbio, int max_gaps, uint8_t *ops, const int64_t *ops_off, int32_t *aln_len, uint8_t *status);
 
-/* ---- FASTQ text in, SAM text out ------------------------------------------------------------------------------------ */
+/* ---- FASTQ text in, SAM text (or BAM records) out ------------------------------------------------------------------- */
 /* The reference's worker takes a chunk of reads from GetNextChunk (src/GetData.cpp:109-143: four getline() calls per record,
  * the name cut out of the header by IdentifyHeaderBegPos / EndPos, mate 2 reverse-complemented), maps it, and prints every
  * record with fprintf (OutputPairedAlignments / OutputSingledAlignments, src/Mapping.cpp:177-315).  A stream does the same for
@@ -330,6 +330,9 @@ int  kg_fragments_batch(kg_index *ix, const char *frag1, const int64_t *off1, co
  * their own chunk, src/Mapping.cpp:716-717): every lane owns a workspace, device text windows, page-locked staging and
  * result buffers and a HIP stream; the calls of one lane must not overlap, different lanes may be driven from different threads.
  * Short reads, plain 4-line FASTQ, the Illumina configuration (not -pacbio).
+ * The records come back as SAM lines or, after kg_stream_set_format(KG_STREAM_FORMAT_BAM), as uncompressed BAM records (SAM/BAM
+ * specification v1, 4.2: block_size first) -- what the reference's -bo makes of the same lines with sam_parse1 / sam_write1
+ * (src/Mapping.cpp:610-620) before BGZF compresses them; compression stays with the caller.
  *
  *   per batch:  fill kg_stream_staging(lane, f) -> kg_stream_upload (any number of pieces) -> kg_stream_parse -> kg_stream_map
  */
@@ -346,6 +349,11 @@ typedef struct {
 } kg_stream_config;
 int   kg_stream_open(kg_index *ix, const kg_stream_config *cfg, kg_stream **out);
 void  kg_stream_close(kg_stream *s);
+/* What kg_stream_map makes of the records: SAM text (the default) or BAM records.  Holds for every later kg_stream_map on all lanes; call it while no
+ * lane is inside a call (the lanes' output buffers grow to what the larger format needs).  An unknown value is KG_ERR_ARG. */
+#define KG_STREAM_FORMAT_SAM 0
+#define KG_STREAM_FORMAT_BAM 1
+int   kg_stream_set_format(kg_stream *s, int format);
 /* page-locked staging buffer of input file `file` (0 / 1) in lane `lane`, *capacity = max_window bytes */
 char *kg_stream_staging(kg_stream *s, int lane, int file, int64_t *capacity);
 /* staging[file][from, to) -> the lane's device window, asynchronously: a caller reads the next piece meanwhile */
@@ -384,9 +392,12 @@ typedef struct {
 } kg_stream_params;
 typedef struct {
 	int64_t n_reads, n_chunks;
-	const char *sam;                 /* the SAM lines of the reads decided on the device, in read order (page-locked, the lane's) */
+	const char *sam;                 /* the SAM lines of the reads decided on the device, in read order (page-locked, the lane's).  KG_STREAM_FORMAT_BAM: their
+	                                    BAM records instead, each behind its block_size, in the same order -- byte for byte what an encoder that parses
+	                                    the printed line makes of it: refID = the contig's index, bin from POS and the CIGAR's reference length,
+	                                    integer tags in the smallest type, qualities 0xFF where the column's length is not l_seq */
 	int64_t sam_bytes;
-	const int64_t *sam_off;          /* [n_reads + 1]: the lines of read r are sam[sam_off[r], sam_off[r+1]) -- empty for a read handed back */
+	const int64_t *sam_off;          /* [n_reads + 1]: the lines (records) of read r are sam[sam_off[r], sam_off[r+1]) -- empty for a read handed back */
 	const kg_aln_record *records;    /* [n_records] as kg_align_batch (the first n_reads are the reads' own) */
 	int64_t n_records;
 	const kg_chunk_stats *chunk_stats;   /* [n_chunks] */
@@ -434,7 +445,7 @@ typedef struct {
 	/* what the alignment stage's lists held, summed over the batches: [0] candidates parked for NW, [1] NW jobs, [2] bytes of their op strings,
 	 * [3] fragment pairs through the 8-mer partition, [4] rescue windows, [5] partition plans, [6] pairs aln_trivial decided start to finish, [7] candidates aln_plan_fast left to aln_plan */
 	double aln_counts[8];
-	/* KG_STREAM_CHECKSUM set (a measurement aid): the SAM text of the batches summed on the device -- [0] the sum of its bytes, [1] its line feeds
+	/* KG_STREAM_CHECKSUM set (a measurement aid): the SAM text (the BAM records: whatever bytes were made) of the batches summed on the device -- [0] the sum of its bytes, [1] its line feeds
 	 * (exact: both stay far below 2^53) -- so that a run whose output is never copied into file pages still names the text it made; else 0 */
 	double text_checksum[2];
 } kg_stream_timing_t;

@@ -27,6 +27,7 @@ KG_OK = 0
 KG_MODE_FAST, KG_MODE_SENSITIVE = 0, 1
 KG_INPUT_ASCII = 0x100   # OR into mode: reads are given as characters, encoded on the device
 KG_SA_SAMPLED, KG_SA_FULL = 0, 1
+KG_STREAM_FORMAT_SAM, KG_STREAM_FORMAT_BAM = 0, 1   # kg_stream_set_format
 KG_SA_AUTO = -1                        # full below 2^32 text symbols; above: wide where the device has room, else compact (the host pipeline's default)
 KG_SA_FULL40 = 5                       # the compact index: 5-byte suffix-array entries, a quarter of the q-mer table, no triple planes
 KG_SA_FULL40_WIDE = 6                  # 5-byte suffix-array entries with the full q-mer table and the triple planes
@@ -44,7 +45,7 @@ ABI_SYMBOLS = (
     "kg_workspace_overflow", "kg_workspace_segment_fallbacks", "kg_workspace_set_profiling", "kg_workspace_set_single_steps", "kg_index_selfcheck", "kg_workspace_kernel_ms", "kg_seed_batch", "kg_candidates_batch", "kg_align_batch", "kg_align_reasons", "kg_seed_batch_device", "kg_nw_batch", "kg_nw_batch_device",
     "kg_fragments_batch", "kg_longread_batch", "kg_longread_reasons",
     "kg_stream_open", "kg_stream_close", "kg_stream_staging", "kg_stream_upload", "kg_stream_parse", "kg_stream_map", "kg_stream_fetch", "kg_stream_fetch_reads", "kg_stream_timing",
-    "kg_stream_group_absent", "kg_stream_group_abort",
+    "kg_stream_group_absent", "kg_stream_group_abort", "kg_stream_set_format",
 )
 
 
@@ -209,6 +210,7 @@ def load_library() -> C.CDLL:
     L.kg_stream_fetch_reads.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.kg_stream_group_absent.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.kg_stream_group_abort.argtypes = [C.c_void_p]
+    L.kg_stream_set_format.argtypes = [C.c_void_p, C.c_int]
     L.kg_stream_timing.argtypes = [C.c_void_p, C.POINTER(StreamTiming), C.c_int]
     _lib = L
     return L
@@ -448,7 +450,9 @@ class Index:
 
 
 class Stream:
-    """kg_stream_*: FASTQ text in, SAM text out (GetNextChunk ... Output*Alignments of the reference on the device)."""
+    """kg_stream_*: FASTQ text in, SAM text or BAM records out (GetNextChunk ... Output*Alignments of the reference on the device)."""
+
+    FORMATS = {"sam": KG_STREAM_FORMAT_SAM, "bam": KG_STREAM_FORMAT_BAM}
 
     def __init__(self, index: "Index", max_reads: int = 16000, max_window: int = 8 << 20, lanes: int = 1, seed_group: int = 0):
         self.lib = load_library()
@@ -463,6 +467,10 @@ class Stream:
         if self.h:
             self.lib.kg_stream_close(self.h)
             self.h = None
+
+    def set_format(self, fmt):
+        """what map() returns per read from here on: "sam" (the default) lines, "bam" uncompressed BAM records (block_size first)"""
+        _check(self.lib.kg_stream_set_format(self.h, self.FORMATS.get(fmt, fmt) if isinstance(fmt, str) else int(fmt)), "kg_stream_set_format")
 
     def group_absent(self, lane: int, rounds: int):
         """seeding groups: lane `lane` has no batch for `rounds` rounds (< 0: until further notice, 0: it takes part again)"""
@@ -501,7 +509,7 @@ class Stream:
         return [raw[off[i]:off[i + 1]] for i in range(parsed.n_reads)]
 
     def map(self, est_distance: int = 1500, max_insert: int = 1500, max_gaps: int = 5, multi_hit: bool = False, unset_flag: int = 0, lane: int = 0):
-        """seeding .. SAM text for the parsed batch: (text per read, indices of the reads handed back)"""
+        """seeding .. SAM text (or BAM records, set_format) for the parsed batch: (bytes per read, indices of the reads handed back)"""
         prm = StreamParams(est_distance, max_insert, max_gaps, 1 if multi_hit else 0, unset_flag, 1)
         res = StreamResult()
         _check(self.lib.kg_stream_map(self.h, lane, C.byref(prm), C.byref(res)), "kg_stream_map")

@@ -1,4 +1,4 @@
-// abi_stream.hip -- kg_stream_*: FASTQ text in, SAM text out (declared in include/kart_amd.h).
+// abi_stream.hip -- kg_stream_*: FASTQ text in, SAM text (or BAM records, kg_stream_set_format) out (declared in include/kart_amd.h).
 //
 // One call chain per batch replaces what the reference's worker loop does for a chunk from GetNextChunk to the fprintf of its SAM
 // lines (src/Mapping.cpp:488-637; src/GetData.cpp:109-143): the caller uploads the bytes of the input files as they lie there,
@@ -129,6 +129,7 @@ struct kg_stream {
 	uint8_t *d_chr_names = nullptr;
 	int32_t *d_chr_name_off = nullptr;
 	int min_seed_len = 13;
+	int format = KG_STREAM_FORMAT_SAM;                 // what kg_stream_map makes of the records (kg_stream_set_format)
 	std::mutex mu;
 	kg_stream_timing_t total{};
 };
@@ -171,6 +172,14 @@ FqWindow window_of(const kg_stream *s, const Lane &l, int f)
 	w.rec_hdr = r; w.rec_name = r + c; w.rec_seq = r + 2 * c; w.rec_qual = r + 3 * c;
 	w.rec_rlen = (int32_t *)(r + 4 * c); w.rec_qlen = (int32_t *)(r + 5 * c);
 	return w;
+}
+
+// bytes of a lane's output buffer.  SAM: a batch's input bytes and a little more per read (FLAG .. TLEN and the tags against '+' and the mate
+// suffix).  BAM: a record of a very short read is larger than its line -- 36 bytes of core, four per CIGAR operation and up to 21 of tags against a
+// few characters of text; over its FASTQ record (name + 2 L + 6 bytes) a record of L bases gains 52 + min(96, 4 L) - L / 2 <= 136 bytes.
+int64_t out_capacity(const kg_stream_config &cfg, int format)
+{
+	return 2 * cfg.max_window + (format == KG_STREAM_FORMAT_BAM ? 144 : 64) * cfg.max_reads + 4096;
 }
 
 float elapsed(hipEvent_t a, hipEvent_t b)
@@ -277,8 +286,7 @@ int kg_stream_open(kg_index *ix, const kg_stream_config *cfg, kg_stream **out)
 		HIP_TRY(hipHostMalloc((void **)&l.h_cand_off, 8 * (size_t)(n + 8), hipHostMallocDefault));
 		HIP_TRY(hipHostMalloc((void **)&l.h_host_list, 4 * (size_t)(n + 8), hipHostMallocDefault));
 		HIP_TRY(hipHostMalloc((void **)&l.h_ctl, 8 * kCtlWords, hipHostMallocDefault));
-		// the text of a batch: its input's bytes and a little more per read (FLAG .. TLEN and the tags against '+' and the mate suffix)
-		l.d_sam_capacity = 2 * cfg->max_window + 64 * n + 4096;
+		l.d_sam_capacity = out_capacity(*cfg, KG_STREAM_FORMAT_SAM);
 		HIP_TRY(hipMalloc((void **)&l.d_sam, (size_t)l.d_sam_capacity));
 		l.h_sam_capacity = l.d_sam_capacity;
 		HIP_TRY(hipHostMalloc((void **)&l.h_sam, (size_t)l.h_sam_capacity, hipHostMallocDefault));
@@ -304,6 +312,31 @@ void kg_stream_close(kg_stream *s)
 	if (s->d_chr_names) (void)hipFree(s->d_chr_names);
 	if (s->d_chr_name_off) (void)hipFree(s->d_chr_name_off);
 	delete s;
+}
+
+int kg_stream_set_format(kg_stream *s, int format)
+{
+	if (!s) return fail(KG_ERR_ARG, "kg_stream_set_format: null stream");
+	if (format != KG_STREAM_FORMAT_SAM && format != KG_STREAM_FORMAT_BAM) return fail(KG_ERR_ARG, "kg_stream_set_format: unknown format %d (KG_STREAM_FORMAT_SAM or KG_STREAM_FORMAT_BAM)", format);
+	HIP_TRY(hipSetDevice(s->ix->device));
+	// the lanes' output buffers hold a batch in the larger of the two formats from the first BAM run on
+	const int64_t want = out_capacity(s->cfg, format);
+	for (Lane &l : s->lanes) {
+		if (l.d_sam_capacity < want) {
+			HIP_TRY(hipStreamSynchronize(l.ws->stream));
+			HIP_TRY(hipFree(l.d_sam)); l.d_sam = nullptr; l.d_sam_capacity = 0;
+			HIP_TRY(hipMalloc((void **)&l.d_sam, (size_t)want));
+			l.d_sam_capacity = want;
+		}
+		if (l.h_sam_capacity < want) {
+			HIP_TRY(hipStreamSynchronize(l.ws->stream));
+			HIP_TRY(hipHostFree(l.h_sam)); l.h_sam = nullptr; l.h_sam_capacity = 0;
+			HIP_TRY(hipHostMalloc((void **)&l.h_sam, (size_t)want, hipHostMallocDefault));
+			l.h_sam_capacity = want;
+		}
+	}
+	s->format = format;
+	return KG_OK;
 }
 
 char *kg_stream_staging(kg_stream *s, int lane, int file, int64_t *capacity)
@@ -551,7 +584,8 @@ int kg_stream_map(kg_stream *s, int lane, const kg_stream_params *prm, kg_stream
 	q.chr_names = s->d_chr_names; q.chr_name_off = s->d_chr_name_off;
 	q.sam_len = l.d_sam_len; q.sam_off = l.d_sam_off; q.sam = l.d_sam; q.sam_capacity = l.d_sam_capacity;
 	q.host_list = l.d_host_list; q.ctl = l.d_sam_ctl;
-	HIP_TRY(launch_sam_size(q, l.d_scan, l.scan_bytes, ix->n_cu, st));
+	const bool bam = s->format == KG_STREAM_FORMAT_BAM;
+	HIP_TRY(bam ? launch_bam_size(q, l.d_scan, l.scan_bytes, ix->n_cu, st) : launch_sam_size(q, l.d_scan, l.scan_bytes, ix->n_cu, st));
 	int64_t *tot = l.h_meta + FQM_WORDS;              // [0] text bytes, [1] reads handed back, [2] format errors, [3] extra records of -m
 	HIP_TRY(hipMemcpyAsync(&tot[0], l.d_sam_off + n, 8, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(&tot[1], l.d_sam_ctl, 8, hipMemcpyDeviceToHost, st));
@@ -580,7 +614,7 @@ int kg_stream_map(kg_stream *s, int lane, const kg_stream_params *prm, kg_stream
 		HIP_TRY(hipHostMalloc((void **)&l.h_cands, sizeof(kg_candidate) * (size_t)l.h_cand_capacity, hipHostMallocDefault));
 		HIP_TRY(hipHostMalloc((void **)&l.h_cand_seeds, sizeof(kg_seed) * (size_t)l.h_cand_capacity, hipHostMallocDefault));
 	}
-	HIP_TRY(launch_sam_format(q, ix->n_cu, st));
+	HIP_TRY(bam ? launch_bam_format(q, ix->n_cu, st) : launch_sam_format(q, ix->n_cu, st));
 	// measurement aid (bench.py's gpu_pipeline leg): the text summed on the device, for runs that never copy it into file pages (read per call: a session switches it on and off)
 	const bool checksum = getenv("KG_STREAM_CHECKSUM") != nullptr;
 	if (checksum) HIP_TRY(launch_sam_checksum(q, ix->n_cu, st));

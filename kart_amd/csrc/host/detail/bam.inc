@@ -156,17 +156,39 @@ bool bam_from_sam_line(const std::map<std::string_view, int> &ref_id, const char
 	return true;
 }
 
+// the SAM lines in text[at, end) -> BAM records appended to raw (a line that is no record is dropped, as sam_parse1 < 0 does)
+void bam_from_sam_text(const Ctx &cx, const std::string &text, size_t at, size_t end, std::string &raw)
+{
+	while (at < end) {
+		const char *nl = (const char *)memchr(text.data() + at, '\n', end - at);
+		size_t e = nl ? (size_t)(nl - text.data()) : end;
+		if (e > at) bam_from_sam_line(cx.bam_ref_id, text.data() + at, e - at, raw);
+		at = e + 1;
+	}
+}
+
+// a chunk of the device stream: `text` holds the lines the HOST printed, piece by piece (len[k] bytes each: the reads the device handed back, the pairs
+// mapped again) -> the same pieces as uncompressed BAM records, len[] updated
+void bam_raw_pieces(const Ctx &cx, std::string &text, std::vector<uint32_t> &len)
+{
+	std::string raw;
+	raw.reserve(text.size());
+	size_t at = 0;
+	for (uint32_t &n : len) {
+		const size_t before = raw.size();
+		bam_from_sam_text(cx, text, at, at + n, raw);
+		at += n;
+		n = (uint32_t)(raw.size() - before);
+	}
+	text.swap(raw);
+}
+
 // the SAM text of a chunk -> BGZF-compressed BAM records (replaces the text in place)
 void bam_encode_chunk(const Ctx &cx, std::string &text)
 {
 	std::string raw, out;
 	raw.reserve(text.size());
-	for (size_t at = 0; at < text.size();) {
-		const char *nl = (const char *)memchr(text.data() + at, '\n', text.size() - at);
-		size_t e = nl ? (size_t)(nl - text.data()) : text.size();
-		if (e > at) bam_from_sam_line(cx.bam_ref_id, text.data() + at, e - at, raw);     // a line that is no record is dropped, as sam_parse1 < 0 does
-		at = e + 1;
-	}
+	bam_from_sam_text(cx, text, 0, text.size(), raw);
 	out.reserve(raw.size() / 3 + 64);
 	bgzf_append(raw, out);
 	text.swap(out);

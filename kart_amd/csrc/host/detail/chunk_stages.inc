@@ -214,7 +214,10 @@ void chunk_stage_c(const Ctx &cx, std::vector<Read> &reads, ChunkState &ck)
 			else if (nh == 0) break;
 		}
 	}
-	if (cx.opt.bam) bam_encode_chunk(cx, ck.text);
+	// -bo: the chunk's text becomes its compressed BAM records here; a chunk of the device stream holds only the host's own lines, which become
+	// raw records -- the device's records around them are joined and compressed once the chunk is committed (stream.inc, BamPacker)
+	if (cx.opt.bam && ck.stream) bam_raw_pieces(cx, ck.text, ck.host_len);
+	else if (cx.opt.bam) bam_encode_chunk(cx, ck.text);
 	ck.text_size = ck.text.size();
 	ck.st.total_reads = ck.count;
 	ck.cands.clear(); ck.work.clear();

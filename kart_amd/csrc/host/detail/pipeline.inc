@@ -218,8 +218,11 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 	// of it) up to the first thing its parser leaves to the reader below -- normally the end of the file.
 	// ... and gz libraries: their text is inflated by threads of their own into a growing block that the stream reads like a mapped file
 	// (Source::gz_stream_begin; KART_AMD_NO_GZ_STREAM: the host's gz reader maps them, as until round 5)
-	if (src.gzfast && !src.fast && !cx.opt.pacbio && !cx.opt.bam && !g_check_align && cx.fastq && cx.kern.has_stream() && !getenv("KART_AMD_NO_GZ_STREAM") && !shard.active()) src.gz_stream_begin();
-	if ((src.fast || src.gzstream) && !cx.opt.pacbio && !cx.opt.bam && !g_check_align && cx.fastq) {
+	// -bo: the device makes the BAM records (kg_stream_set_format) and the committed chunks are compressed beside the commit (BamPacker); a sharded
+	// -bo run keeps the host's reader and encoder (a deferred shard holds text it may have to map again)
+	const bool bam_by_host = cx.opt.bam && shard.active();
+	if (src.gzfast && !src.fast && !cx.opt.pacbio && !g_check_align && cx.fastq && cx.kern.has_stream() && !getenv("KART_AMD_NO_GZ_STREAM") && !shard.active()) src.gz_stream_begin();
+	if ((src.fast || src.gzstream) && !cx.opt.pacbio && !bam_by_host && !g_check_align && cx.fastq) {
 		// window per file: the records of a full batch and half as much again (the first quarter of a staging buffer holds the
 		// unconsumed tail of the batch before)
 		double bpr = 0;
@@ -258,6 +261,7 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 		int lanes = lanes_env > 0 ? std::min(lanes_env, 16) : (group ? 2 * group : 4);      // (independent lanes, six writers: 3 lanes 0.75-0.79 s per 20 M reads, 4 0.73 s, 5 0.72-0.73 s)
 		if (group && lanes % group != 0) lanes = (lanes + group - 1) / group * group;
 		if (StreamBackend *sb = cx.kern.stream(full_reads + full_reads / 4 + chunk_limit, window, lanes, group)) {
+			sb->set_format(cx.opt.bam);                 // (the stream is the session's: a -o run may follow a -bo run)
 			Options &o = const_cast<Options &>(cx.opt);
 			const int64_t keep = o.batch_reads;
 			o.batch_reads = full_reads;

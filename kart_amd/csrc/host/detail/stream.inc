@@ -1,4 +1,4 @@
-// host/detail/stream.inc -- one library through the device's FASTQ-in / SAM-out stream: the host only moves bytes.
+// host/detail/stream.inc -- one library through the device's FASTQ-in / SAM-out (-bo: BAM-out) stream: the host only moves bytes (and deflates them).
 // A fragment of mapper.cpp (included there, inside namespace kart { namespace { ... } }); not a translation unit of its own.
 // ----------------------------------------------------------------------------------------------
 // The reference's worker reads a chunk with getline() (GetNextChunk, src/GetData.cpp:109-143), maps it and prints its records with
@@ -87,6 +87,94 @@ private:
 	std::vector<Group *> groups_;
 	std::vector<std::thread> th_;
 	bool stop_ = false;
+};
+
+// -bo: the committed chunks of a run whose records the device makes as BAM (kg_stream_set_format).  A chunk's raw BAM is its pieces joined -- the
+// device's records out of the lane's buffer, the host's own records (bam_raw_pieces) between them -- and is compressed as one series of BGZF blocks
+// per chunk: what bam_encode_chunk makes of the same chunk's text on the host's path, so the file is the same byte for byte.  Deflate is the run's
+// largest cost on the host, so it runs on threads of its own beside the commit.  The file's order is the chunks' order, and a chunk's place in the
+// file is known only once every chunk before it has been compressed: whoever finishes the next chunk in line hands it -- and the finished ones
+// behind it -- to the writer.
+class BamPacker {
+public:
+	BamPacker(Writer *writer, int n_threads, std::mutex *done_mu, std::condition_variable *done_cv) : writer_(writer), done_mu_(done_mu), done_cv_(done_cv)
+	{
+		for (int t = 0; t < std::max(1, n_threads); ++t) th_.emplace_back([this]() { loop(); });
+	}
+	~BamPacker() { finish(); }
+	// the pieces stay where they are until *pending has been decremented (under *done_mu): the lane's buffers are free again once the chunk is joined
+	void push(std::vector<TextPiece> &&pieces, size_t total, std::string &&hold, std::atomic<int> *pending)
+	{
+		std::lock_guard<std::mutex> lk(mu_);
+		q_.emplace_back();
+		Job &j = q_.back();
+		j.seq = pushed_++; j.pieces = std::move(pieces); j.total = total; j.hold = std::move(hold); j.pending = pending;
+		cv_.notify_one();
+	}
+	// every chunk pushed so far is with the writer when this returns
+	void finish()
+	{
+		{
+			std::lock_guard<std::mutex> lk(mu_);
+			stop_ = true;
+		}
+		cv_.notify_all();
+		for (std::thread &t : th_) t.join();
+		th_.clear();
+	}
+	int64_t bytes() const { return bytes_; }
+
+private:
+	struct Job {
+		int64_t seq = 0;
+		std::vector<TextPiece> pieces;
+		size_t total = 0;
+		std::string hold;
+		std::atomic<int> *pending = nullptr;
+	};
+	void loop()
+	{
+		for (;;) {
+			Job j;
+			{
+				std::unique_lock<std::mutex> lk(mu_);
+				cv_.wait(lk, [this]() { return stop_ || !q_.empty(); });
+				if (q_.empty()) return;
+				j = std::move(q_.front());
+				q_.pop_front();
+			}
+			std::string raw, out;
+			raw.reserve(j.total);
+			size_t hold_at = 0;
+			for (const TextPiece &tp : j.pieces) {
+				if (tp.p) raw.append(tp.p, tp.n);
+				else { raw.append(j.hold.data() + hold_at, tp.n); hold_at += tp.n; }
+			}
+			{
+				std::lock_guard<std::mutex> lk(*done_mu_);
+				j.pending->fetch_sub(1);
+				done_cv_->notify_all();
+			}
+			out.reserve(raw.size() / 3 + 64);
+			bgzf_append(raw, out);
+			std::lock_guard<std::mutex> lk(mu_);
+			ready_[j.seq] = std::move(out);
+			for (std::map<int64_t, std::string>::iterator it = ready_.begin(); it != ready_.end() && it->first == next_; it = ready_.erase(it), ++next_) {
+				bytes_ += (int64_t)it->second.size();
+				writer_->push(std::move(it->second));
+			}
+		}
+	}
+	Writer *writer_;
+	std::mutex *done_mu_;
+	std::condition_variable *done_cv_;
+	std::mutex mu_;
+	std::condition_variable cv_;
+	std::deque<Job> q_;
+	std::map<int64_t, std::string> ready_;      // compressed chunks that wait for one before them
+	int64_t pushed_ = 0, next_ = 0, bytes_ = 0;
+	bool stop_ = false;
+	std::vector<std::thread> th_;
 };
 
 // one batch in a lane
@@ -246,6 +334,9 @@ bool map_library_stream(Ctx &cx, Source &src, StreamBackend &sb, Writer *writer,
 	}
 	const int host_threads = std::max(1, cx.opt.threads / 2);
 	TaskPool pool(host_threads, 5);
+	// -bo: the whole thread budget compresses (the lane threads wait for the device, the pool for the few reads handed back, the writers for the packer)
+	std::unique_ptr<BamPacker> packer;
+	if (cx.opt.bam && writer && !held) packer.reset(new BamPacker(writer, std::max(1, cx.opt.threads), &feed.mu, &feed.cv));
 	std::vector<std::unique_ptr<StreamBatch>> batches;
 	for (int l = 0; l < K; ++l) { batches.emplace_back(new StreamBatch()); batches.back()->lane = l; }
 	const bool verbose = getenv("KART_AMD_VERBOSE") != nullptr;
@@ -566,7 +657,8 @@ bool map_library_stream(Ctx &cx, Source &src, StreamBackend &sb, Writer *writer,
 					st.total_reads += ck.count;
 					st.unmapped += ck.st.unmapped;
 					st.unique += ck.st.unique;
-					writer->push_pieces(std::move(pieces), total, std::move(ck.text), &b.writes_pending, &feed.mu, &feed.cv);
+					if (packer) packer->push(std::move(pieces), total, std::move(ck.text), &b.writes_pending);
+					else writer->push_pieces(std::move(pieces), total, std::move(ck.text), &b.writes_pending, &feed.mu, &feed.cv);
 				}
 			}
 			est_latest.store(est_speculated(cx, shard, tot.iPaired, tot.iDistance));
@@ -594,6 +686,7 @@ bool map_library_stream(Ctx &cx, Source &src, StreamBackend &sb, Writer *writer,
 			return true;
 		});
 	}
+	if (packer) packer->finish();              // (the caller's own reader and writer may continue behind the stream's last chunk)
 	src.m1.pos = feed.pos[0];
 	if (src.sep) src.m2.pos = feed.pos[1];
 	{

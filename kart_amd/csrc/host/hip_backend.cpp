@@ -66,6 +66,10 @@ public:
 	{
 		if (kg_stream_group_absent(s_, lane, rounds) != KG_OK) die("kg_stream_group_absent");
 	}
+	void set_format(bool bam) override
+	{
+		if (kg_stream_set_format(s_, bam ? KG_STREAM_FORMAT_BAM : KG_STREAM_FORMAT_SAM) != KG_OK) die("kg_stream_set_format");
+	}
 	kg_stream *handle() const { return s_; }
 
 private:
