@@ -329,7 +329,10 @@ int  kg_fragments_batch(kg_index *ix, const char *frag1, const int64_t *off1, co
  * and receives the text of the SAM records.  `lanes` batches are in flight at once (the reference's N worker threads each on
  * their own chunk, src/Mapping.cpp:716-717): every lane owns a workspace, device text windows, page-locked staging and
  * result buffers and a HIP stream; the calls of one lane must not overlap, different lanes may be driven from different threads.
- * Short reads, plain 4-line FASTQ, the Illumina configuration (not -pacbio).
+ * Short reads, the Illumina configuration (not -pacbio).  Input: plain 4-line FASTQ (the default), or -- after
+ * kg_stream_set_input(KG_STREAM_INPUT_FASTA) -- FASTA as GetNextEntry reads it with FastQFormat == false (src/GetData.cpp:76-104): the first line
+ * of an entry is its header, every further line up to the next one whose first byte is '>' adds its characters but the last (taken to be the
+ * newline) to the sequence; the quality column of every record is then "*".  The inflated text of a gz file of either format: kg_stream_window::gz_lines.
  * The records come back as SAM lines or, after kg_stream_set_format(KG_STREAM_FORMAT_BAM), as uncompressed BAM records (SAM/BAM
  * specification v1, 4.2: block_size first) -- what the reference's -bo makes of the same lines with sam_parse1 / sam_write1
  * (src/Mapping.cpp:610-620) before BGZF compresses them; compression stays with the caller.
@@ -354,6 +357,11 @@ void  kg_stream_close(kg_stream *s);
 #define KG_STREAM_FORMAT_SAM 0
 #define KG_STREAM_FORMAT_BAM 1
 int   kg_stream_set_format(kg_stream *s, int format);
+/* What kg_stream_parse takes the text for: FASTQ (the default) or FASTA.  Holds for every later kg_stream_parse on all lanes; call it while no lane is
+ * inside a call (the first FASTA run allocates the per-line arrays of its record kernels).  An unknown value is KG_ERR_ARG. */
+#define KG_STREAM_INPUT_FASTQ 0
+#define KG_STREAM_INPUT_FASTA 1
+int   kg_stream_set_input(kg_stream *s, int input);
 /* page-locked staging buffer of input file `file` (0 / 1) in lane `lane`, *capacity = max_window bytes */
 char *kg_stream_staging(kg_stream *s, int lane, int file, int64_t *capacity);
 /* staging[file][from, to) -> the lane's device window, asynchronously: a caller reads the next piece meanwhile */
@@ -368,7 +376,8 @@ typedef struct {
 	int32_t gz_lines;            /* != 0: the text was inflated from a gz file, which the reference reads through gzgets() with a 1000-byte buffer
 	                                (src/GetData.cpp:145-219): a record with a line of more than 999 bytes (its newline included), or whose header line
 	                                does not start with '@' / '>' or names nothing (:162), is read differently there -- it ends the batch
-	                                (KG_STREAM_STOP_IRREGULAR) and the caller's gz reader continues in front of it */
+	                                (KG_STREAM_STOP_IRREGULAR) and the caller's gz reader continues in front of it.  FASTA: gzGetNextEntry takes exactly
+	                                one sequence line per entry (:160-167), so a record with none or several ends the batch as well */
 	int64_t want_reads;          /* take at most this many reads (a multiple of chunk_reads, <= max_reads) */
 } kg_stream_window;
 #define KG_STREAM_STOP_NONE      0

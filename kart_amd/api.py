@@ -28,6 +28,7 @@ KG_MODE_FAST, KG_MODE_SENSITIVE = 0, 1
 KG_INPUT_ASCII = 0x100   # OR into mode: reads are given as characters, encoded on the device
 KG_SA_SAMPLED, KG_SA_FULL = 0, 1
 KG_STREAM_FORMAT_SAM, KG_STREAM_FORMAT_BAM = 0, 1   # kg_stream_set_format
+KG_STREAM_INPUT_FASTQ, KG_STREAM_INPUT_FASTA = 0, 1   # kg_stream_set_input
 KG_SA_AUTO = -1                        # full below 2^32 text symbols; above: wide where the device has room, else compact (the host pipeline's default)
 KG_SA_FULL40 = 5                       # the compact index: 5-byte suffix-array entries, a quarter of the q-mer table, no triple planes
 KG_SA_FULL40_WIDE = 6                  # 5-byte suffix-array entries with the full q-mer table and the triple planes
@@ -45,7 +46,7 @@ ABI_SYMBOLS = (
     "kg_workspace_overflow", "kg_workspace_segment_fallbacks", "kg_workspace_set_profiling", "kg_workspace_set_single_steps", "kg_index_selfcheck", "kg_workspace_kernel_ms", "kg_seed_batch", "kg_candidates_batch", "kg_align_batch", "kg_align_reasons", "kg_seed_batch_device", "kg_nw_batch", "kg_nw_batch_device",
     "kg_fragments_batch", "kg_longread_batch", "kg_longread_reasons",
     "kg_stream_open", "kg_stream_close", "kg_stream_staging", "kg_stream_upload", "kg_stream_parse", "kg_stream_map", "kg_stream_fetch", "kg_stream_fetch_reads", "kg_stream_timing",
-    "kg_stream_group_absent", "kg_stream_group_abort", "kg_stream_set_format",
+    "kg_stream_group_absent", "kg_stream_group_abort", "kg_stream_set_format", "kg_stream_set_input",
 )
 
 
@@ -211,6 +212,7 @@ def load_library() -> C.CDLL:
     L.kg_stream_group_absent.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.kg_stream_group_abort.argtypes = [C.c_void_p]
     L.kg_stream_set_format.argtypes = [C.c_void_p, C.c_int]
+    L.kg_stream_set_input.argtypes = [C.c_void_p, C.c_int]
     L.kg_stream_timing.argtypes = [C.c_void_p, C.POINTER(StreamTiming), C.c_int]
     _lib = L
     return L
@@ -450,9 +452,10 @@ class Index:
 
 
 class Stream:
-    """kg_stream_*: FASTQ text in, SAM text or BAM records out (GetNextChunk ... Output*Alignments of the reference on the device)."""
+    """kg_stream_*: FASTQ or FASTA text in, SAM text or BAM records out (GetNextChunk ... Output*Alignments of the reference on the device)."""
 
     FORMATS = {"sam": KG_STREAM_FORMAT_SAM, "bam": KG_STREAM_FORMAT_BAM}
+    INPUTS = {"fastq": KG_STREAM_INPUT_FASTQ, "fasta": KG_STREAM_INPUT_FASTA}
 
     def __init__(self, index: "Index", max_reads: int = 16000, max_window: int = 8 << 20, lanes: int = 1, seed_group: int = 0):
         self.lib = load_library()
@@ -472,6 +475,11 @@ class Stream:
         """what map() returns per read from here on: "sam" (the default) lines, "bam" uncompressed BAM records (block_size first)"""
         _check(self.lib.kg_stream_set_format(self.h, self.FORMATS.get(fmt, fmt) if isinstance(fmt, str) else int(fmt)), "kg_stream_set_format")
 
+    def set_input(self, kind):
+        """what parse() takes the text for from here on: "fastq" (the default, four lines per record) or "fasta" (a header line, then sequence lines
+        up to the next line that starts with '>'; the quality column of every record is "*")"""
+        _check(self.lib.kg_stream_set_input(self.h, self.INPUTS.get(kind, -1) if isinstance(kind, str) else int(kind)), "kg_stream_set_input")
+
     def group_absent(self, lane: int, rounds: int):
         """seeding groups: lane `lane` has no batch for `rounds` rounds (< 0: until further notice, 0: it takes part again)"""
         _check(self.lib.kg_stream_group_absent(self.h, lane, rounds), "kg_stream_group_absent")
@@ -481,8 +489,9 @@ class Stream:
         _check(self.lib.kg_stream_group_abort(self.h), "kg_stream_group_abort")
 
     def parse(self, text1: bytes, text2: bytes | None = None, paired: bool = True, chunk_reads: int = 4000, want_reads: int | None = None,
-              eof=(True, True), begin=(0, 0), lane: int = 0) -> StreamParsed:
-        """uploads the window(s) (placed at staging offset begin[f]) and runs GetNextChunk's arithmetic on the device"""
+              eof=(True, True), begin=(0, 0), lane: int = 0, gz_lines: int = 0) -> StreamParsed:
+        """uploads the window(s) (placed at staging offset begin[f]) and runs GetNextChunk's arithmetic on the device; gz_lines: the text is taken
+        for the inflated text of a gz file (kg_stream_window::gz_lines: a record gzgets() reads differently ends the batch)"""
         w = StreamWindow()
         texts = [text1] + ([text2] if text2 is not None else [])
         for f, t in enumerate(texts):
@@ -495,6 +504,7 @@ class Stream:
         w.two_files = 1 if text2 is not None else 0
         w.paired = 1 if paired else 0
         w.chunk_reads = chunk_reads
+        w.gz_lines = 1 if gz_lines else 0
         w.want_reads = want_reads if want_reads is not None else chunk_reads
         out = StreamParsed()
         _check(self.lib.kg_stream_parse(self.h, lane, C.byref(w), C.byref(out)), "kg_stream_parse")

@@ -1,4 +1,4 @@
-// abi_stream.hip -- kg_stream_*: FASTQ text in, SAM text (or BAM records, kg_stream_set_format) out (declared in include/kart_amd.h).
+// abi_stream.hip -- kg_stream_*: FASTQ or FASTA text in, SAM text (or BAM records, kg_stream_set_format) out (declared in include/kart_amd.h).
 //
 // One call chain per batch replaces what the reference's worker loop does for a chunk from GetNextChunk to the fprintf of its SAM
 // lines (src/Mapping.cpp:488-637; src/GetData.cpp:109-143): the caller uploads the bytes of the input files as they lie there,
@@ -26,6 +26,8 @@ struct Lane {
 	int32_t *d_tile[2] = {nullptr, nullptr};
 	uint32_t *d_line_end[2] = {nullptr, nullptr};
 	uint32_t *d_rec[2] = {nullptr, nullptr};           // six arrays of rec_capacity words: hdr, name, seq, qual, rlen, qlen
+	uint64_t *d_line_acc[2] = {nullptr, nullptr};      // FASTA (allocated by the first kg_stream_set_input(FASTA)): [line_capacity + 1] per-line record / character counts
+	uint32_t *d_rec_line[2] = {nullptr, nullptr};      // ... and [rec_capacity + 1] the header line of every record
 	int64_t *d_meta = nullptr;
 	int32_t *d_read_len = nullptr;
 	void *d_scan = nullptr;
@@ -57,6 +59,7 @@ struct Lane {
 	kg_stream_window win{};
 	kg_stream_parsed parsed{};
 	bool have_batch = false;
+	bool fasta = false;                                // the lane's parsed batch came from FASTA text (no qualities)
 	hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 	hipEvent_t ev_parsed = nullptr;                    // the batch is materialised and published to its group (recorded on the lane's stream)
 };
@@ -130,6 +133,8 @@ struct kg_stream {
 	int32_t *d_chr_name_off = nullptr;
 	int min_seed_len = 13;
 	int format = KG_STREAM_FORMAT_SAM;                 // what kg_stream_map makes of the records (kg_stream_set_format)
+	int input = KG_STREAM_INPUT_FASTQ;                 // what kg_stream_parse takes the text for (kg_stream_set_input)
+	bool fasta_sized = false;                          // the record tables hold line_capacity / 2 records (a FASTA record can be two lines) and the FASTA arrays exist
 	std::mutex mu;
 	kg_stream_timing_t total{};
 };
@@ -146,6 +151,8 @@ void free_lane(Lane &l)
 		if (l.d_tile[f]) (void)hipFree(l.d_tile[f]);
 		if (l.d_line_end[f]) (void)hipFree(l.d_line_end[f]);
 		if (l.d_rec[f]) (void)hipFree(l.d_rec[f]);
+		if (l.d_line_acc[f]) (void)hipFree(l.d_line_acc[f]);
+		if (l.d_rec_line[f]) (void)hipFree(l.d_rec_line[f]);
 		if (l.h_text[f]) (void)hipHostFree(l.h_text[f]);
 		if (l.h_rec_hdr[f]) (void)hipHostFree(l.h_rec_hdr[f]);
 	}
@@ -171,6 +178,8 @@ FqWindow window_of(const kg_stream *s, const Lane &l, int f)
 	const size_t c = (size_t)s->rec_capacity;
 	w.rec_hdr = r; w.rec_name = r + c; w.rec_seq = r + 2 * c; w.rec_qual = r + 3 * c;
 	w.rec_rlen = (int32_t *)(r + 4 * c); w.rec_qlen = (int32_t *)(r + 5 * c);
+	w.rec_capacity = s->rec_capacity;
+	w.line_acc = l.d_line_acc[f]; w.rec_line = l.d_rec_line[f];
 	return w;
 }
 
@@ -339,6 +348,43 @@ int kg_stream_set_format(kg_stream *s, int format)
 	return KG_OK;
 }
 
+int kg_stream_set_input(kg_stream *s, int input)
+{
+	if (!s) return fail(KG_ERR_ARG, "kg_stream_set_input: null stream");
+	if (input != KG_STREAM_INPUT_FASTQ && input != KG_STREAM_INPUT_FASTA) return fail(KG_ERR_ARG, "kg_stream_set_input: unknown input %d (KG_STREAM_INPUT_FASTQ or KG_STREAM_INPUT_FASTA)", input);
+	HIP_TRY(hipSetDevice(s->ix->device));
+	if (input == KG_STREAM_INPUT_FASTA) {
+		// the per-line arrays of the FASTA record kernels, and room for their scan, from the first FASTA run on
+		// The record tables were sized for four-line records (line_capacity / 4); a FASTA record can be two lines.  A window with more records than
+		// that -- a header with nothing behind it is a record of ONE line -- goes back to the caller's reader (FQ_STOP_IRREGULAR), as one with too many lines
+		const size_t want_scan = fa_scan_temp_bytes(s->line_capacity);
+		const int64_t rec_capacity = s->line_capacity / 2 + 1;
+		for (Lane &l : s->lanes) {
+			if (s->fasta_sized) break;
+			HIP_TRY(hipStreamSynchronize(l.ws->stream));
+			for (int f = 0; f < 2; ++f) {
+				uint32_t *wider = nullptr;                 // (the old table stays until the new one exists: a failure leaves the stream usable for FASTQ)
+				HIP_TRY(hipMalloc((void **)&wider, 4 * 6 * (size_t)rec_capacity));
+				(void)hipFree(l.d_rec[f]);
+				l.d_rec[f] = wider;
+				if (!l.d_line_acc[f]) HIP_TRY(hipMalloc((void **)&l.d_line_acc[f], 8 * (size_t)(s->line_capacity + 1)));
+				if (!l.d_rec_line[f]) HIP_TRY(hipMalloc((void **)&l.d_rec_line[f], 4 * (size_t)(rec_capacity + 1)));
+				HIP_TRY(hipMemset(l.d_line_acc[f], 0, 8 * (size_t)(s->line_capacity + 1)));
+				HIP_TRY(hipMemset(l.d_rec_line[f], 0, 4 * (size_t)(rec_capacity + 1)));
+			}
+			if (l.scan_bytes < want_scan) {
+				HIP_TRY(hipStreamSynchronize(l.ws->stream));
+				HIP_TRY(hipFree(l.d_scan)); l.d_scan = nullptr; l.scan_bytes = 0;
+				HIP_TRY(hipMalloc(&l.d_scan, want_scan));
+				l.scan_bytes = want_scan;
+			}
+		}
+	}
+	if (input == KG_STREAM_INPUT_FASTA && !s->fasta_sized) { s->rec_capacity = s->line_capacity / 2 + 1; s->fasta_sized = true; }
+	s->input = input;
+	return KG_OK;
+}
+
 char *kg_stream_staging(kg_stream *s, int lane, int file, int64_t *capacity)
 {
 	if (!s || lane < 0 || lane >= (int)s->lanes.size() || file < 0 || file > 1) return nullptr;
@@ -369,6 +415,7 @@ int kg_stream_parse(kg_stream *s, int lane, const kg_stream_window *w, kg_stream
 	HIP_TRY(hipSetDevice(s->ix->device));
 	l.win = *w;
 	l.have_batch = false;
+	l.fasta = s->input == KG_STREAM_INPUT_FASTA;
 	kg_workspace *ws = l.ws;
 	FqArgs a;
 	a.w[0] = window_of(s, l, 0);
@@ -377,6 +424,7 @@ int kg_stream_parse(kg_stream *s, int lane, const kg_stream_window *w, kg_stream
 	a.two_files = w->two_files ? 1 : 0;
 	a.paired = w->paired ? 1 : 0;
 	a.chunk_reads = w->chunk_reads;
+	a.fasta = s->input == KG_STREAM_INPUT_FASTA ? 1 : 0;
 	a.gz_lines = w->gz_lines ? 1 : 0;
 	a.max_reads = s->cfg.max_reads;
 	a.want_reads = w->want_reads;
@@ -579,6 +627,7 @@ int kg_stream_map(kg_stream *s, int lane, const kg_stream_params *prm, kg_stream
 	SamArgs q;
 	q.w[0] = window_of(s, l, 0); q.w[1] = window_of(s, l, 1);
 	q.two_files = l.win.two_files ? 1 : 0; q.paired = l.win.paired ? 1 : 0;
+	q.fasta = l.fasta ? 1 : 0;
 	q.enc = ws->d_enc; q.read_off = ws->d_read_off; q.n_reads = n;
 	q.records = a.records;
 	q.chr_names = s->d_chr_names; q.chr_name_off = s->d_chr_name_off;

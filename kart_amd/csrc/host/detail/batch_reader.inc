@@ -426,6 +426,7 @@ struct Source {
 	bool gzstream = false;     // a gz library on its way through the device stream: m1 / m2 are the growing texts of p1 / p2
 	size_t gz_packed[2] = {0, 0};
 	bool sep = false, fast = false, gzfast = false;
+	bool fasta_fast = false;   // plain FASTA: m1 / m2 map the files for the device stream; the getline() reader continues wherever that one stops
 	double rec_bytes = 400;          // text bytes per record and file, as the batches so far found them (what the parallel line index is sized by)
 	Input in1, in2;            // getline()/gzgets() readers (FASTA, gz)
 	MappedFile m1, m2;         // mapped plain FASTQ, or the inflated text of the current batch
@@ -530,6 +531,19 @@ bool gz_text_regular(const MappedFile &f, size_t buf_size)
 	return f.size - from <= limit;                          // (the unfinished line at the end of the window)
 }
 
+// the line reader of a gz library from the first byte nobody has taken yet: `unparsed` bytes in front of what the inflater has delivered
+// (a fresh stream with zlib's default buffers, as the reference opens it: what gzgets() still delivers of a damaged
+//  stream depends on them, and the one in use may have failed under gzread() already)
+bool gz_reopen_for_lines(Input &in, GzText &g, size_t unparsed)
+{
+	gzFile f = gzopen(g.path.c_str(), "rb");
+	if (!f) return false;
+	if (g.f == in.gz) g.f = nullptr;
+	if (in.gz) gzclose(in.gz);
+	in.gz = f;
+	return gzseek(f, (z_off_t)(g.delivered - unparsed), SEEK_SET) >= 0;
+}
+
 void read_batch(const Ctx &cx, Source &src, int64_t batch_chunks, int chunk_limit, Pool &pool, Batch &b)
 {
 	double t0 = now_s();
@@ -537,6 +551,17 @@ void read_batch(const Ctx &cx, Source &src, int64_t batch_chunks, int chunk_limi
 	std::vector<RecView> &views = b.views;
 	views.clear();
 	int64_t parse_chunks = batch_chunks;
+	if (src.gzfast && !cx.fastq) {
+		// gz FASTA: the inflater serves the device stream only.  What that one left (GzText::carry, Source::gz_stream_end) is the line reader's --
+		// nothing, normally: the library ended with the stream
+		const bool all1 = src.g1.eof && src.g1.delivered > 0 && src.g1.carry.empty(), all2 = !src.sep || (src.g2.eof && src.g2.delivered > 0 && src.g2.carry.empty());
+		if (all1 && all2) src.in1.ended = src.in2.ended = true;
+		else if (!gz_reopen_for_lines(src.in1, src.g1, src.g1.carry.size()) || (src.sep && !gz_reopen_for_lines(src.in2, src.g2, src.g2.carry.size())))
+			run_fail("cannot reposition the gz input for its line reader");
+		src.gzfast = false;
+		src.g1.close_bgzf(); src.g2.close_bgzf();
+		src.g1.carry.clear(); src.g2.carry.clear();
+	}
 	if (src.gzfast) {
 		const size_t recs_per_file = (size_t)batch_chunks * (size_t)chunk_limit / (src.sep ? 2 : 1);
 		b.text1.swap(src.g1.carry); src.g1.carry.clear();
@@ -569,17 +594,7 @@ void read_batch(const Ctx &cx, Source &src, int64_t batch_chunks, int chunk_limi
 			const size_t gz_buf = cx.opt.pacbio ? 1000000 : 1000;
 			if (!gz_text_regular(src.m1, gz_buf) || (src.sep && !gz_text_regular(src.m2, gz_buf))) {
 				// the rest of the library line by line, from the first byte no chunk has taken yet (nothing of this window has been parsed)
-				// (a fresh stream with zlib's default buffers, as the reference opens it: what gzgets() still delivers of a damaged
-				//  stream depends on them, and the one in use may have failed under gzread() already)
-				auto reopen = [](Input &in, GzText &g, size_t unparsed) {
-					gzFile f = gzopen(g.path.c_str(), "rb");
-					if (!f) return false;
-					if (g.f == in.gz) g.f = nullptr;
-					if (in.gz) gzclose(in.gz);
-					in.gz = f;
-					return gzseek(f, (z_off_t)(g.delivered - unparsed), SEEK_SET) >= 0;
-				};
-				if (!reopen(src.in1, src.g1, b.text1.size()) || (src.sep && !reopen(src.in2, src.g2, b.text2.size())))
+				if (!gz_reopen_for_lines(src.in1, src.g1, b.text1.size()) || (src.sep && !gz_reopen_for_lines(src.in2, src.g2, b.text2.size())))
 					run_fail("cannot reposition the gz input for its line reader");
 				src.gzfast = false;
 				src.g1.close_bgzf(); src.g2.close_bgzf();

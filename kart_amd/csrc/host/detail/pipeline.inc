@@ -221,8 +221,9 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 	// -bo: the device makes the BAM records (kg_stream_set_format) and the committed chunks are compressed beside the commit (BamPacker); a sharded
 	// -bo run keeps the host's reader and encoder (a deferred shard holds text it may have to map again)
 	const bool bam_by_host = cx.opt.bam && shard.active();
-	if (src.gzfast && !src.fast && !cx.opt.pacbio && !g_check_align && cx.fastq && cx.kern.has_stream() && !getenv("KART_AMD_NO_GZ_STREAM") && !shard.active()) src.gz_stream_begin();
-	if ((src.fast || src.gzstream) && !cx.opt.pacbio && !bam_by_host && !g_check_align && cx.fastq) {
+	// FASTA (kg_stream_set_input): plain files mapped for the stream (Source::fasta_fast) and gz alike; a sharded run keeps the general reader
+	if (src.gzfast && !src.fast && !cx.opt.pacbio && !g_check_align && cx.kern.has_stream() && !getenv("KART_AMD_NO_GZ_STREAM") && !shard.active()) src.gz_stream_begin();
+	if ((src.fast || (src.fasta_fast && !shard.active()) || src.gzstream) && !cx.opt.pacbio && !bam_by_host && !g_check_align) {
 		// window per file: the records of a full batch and half as much again (the first quarter of a staging buffer holds the
 		// unconsumed tail of the batch before)
 		double bpr = 0;
@@ -232,7 +233,8 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 			size_t lo = mf.pos, hi = std::min(mf.size, lo + ((size_t)1 << 18));
 			int64_t lines = 0, blank = 0;
 			count_lines(mf.data, lo, hi, lines, blank);
-			bpr = std::max(bpr, lines >= 8 ? 4.0 * (double)(hi - lo) / (double)lines : 400.0);
+			// (FASTA: a record is a header line and what follows it)
+			bpr = std::max(bpr, !cx.fastq ? fasta_bytes_per_record(mf.data, lo, hi) : lines >= 8 ? 4.0 * (double)(hi - lo) / (double)lines : 400.0);
 		}
 		// batches of 1 M reads (KART_AMD_STREAM_READS).  A search launch costs ~0.65 ms + 0.52 ms per M reads (1 M reads 1.21 ms, 2 M 1.75 ms,
 		// 4 M 2.94 ms, 20 M 11.0 ms -- alone on the device, the same as inside a run), so larger batches spend less in the search (roofline.frac
@@ -262,6 +264,7 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 		if (group && lanes % group != 0) lanes = (lanes + group - 1) / group * group;
 		if (StreamBackend *sb = cx.kern.stream(full_reads + full_reads / 4 + chunk_limit, window, lanes, group)) {
 			sb->set_format(cx.opt.bam);                 // (the stream is the session's: a -o run may follow a -bo run)
+			sb->set_input(!cx.fastq);                   // (... and a FASTQ library a FASTA one)
 			Options &o = const_cast<Options &>(cx.opt);
 			const int64_t keep = o.batch_reads;
 			o.batch_reads = full_reads;
@@ -270,6 +273,10 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 			(void)all;       // (false: the reader below continues at src.m1.pos / src.m2.pos; true: it finds the files exhausted)
 		}
 		if (src.gzstream) src.gz_stream_end();      // (the gz reader below continues with the text the stream left -- none, normally)
+		if (src.fasta_fast) {                       // the getline() reader below continues where the stream stopped -- at the end of the files, normally
+			fseeko(src.in1.fp, (off_t)src.m1.pos, SEEK_SET);
+			if (src.sep) fseeko(src.in2.fp, (off_t)src.m2.pos, SEEK_SET);
+		}
 	}
 	std::unique_ptr<Batch> nn = fresh();         // cur: device stage done, being mapped; nxt: read, device stage runs now; nn: being read
 	read_stage(cur.get(), batch_chunks);

@@ -9,6 +9,7 @@ struct Input {
 	char *line = nullptr;
 	size_t cap = 0;
 	std::vector<char> gzbuf;
+	bool ended = false;            // the device stream took the library to its end: nothing is left for this reader
 	~Input() { close(); }
 	void close()
 	{
@@ -99,6 +100,7 @@ bool next_entry_gz(Input &in, bool fastq, bool pacbio, OwnedRead &rd)  // gzGetN
 
 bool next_entry(Input &in, bool fastq, bool pacbio, OwnedRead &rd)
 {
+	if (in.ended) return false;
 	return in.gz ? next_entry_gz(in, fastq, pacbio, rd) : next_entry_plain(in, fastq, rd);
 }
 
@@ -241,6 +243,66 @@ bool view_next(MappedFile &f, RecView &v)
 	if ((got = f.line(p)) != -1) { held = p; held_len = got; }
 	v.qual = held; v.qual_len = (int)held_len;
 	return true;
+}
+
+// ---- FASTA on a mapped text (the device stream, stream.inc) ----
+// bytes per record of a FASTA text, from the header lines (first byte '>') in [lo, hi); fewer than two: the default
+double fasta_bytes_per_record(const char *data, size_t lo, size_t hi)
+{
+	int64_t headers = 0;
+	for (const char *p = data + lo, *e = data + hi; p < e;) {
+		if (*p == '>') headers++;
+		const char *nl = (const char *)memchr(p, '\n', (size_t)(e - p));
+		if (!nl) break;
+		p = nl + 1;
+	}
+	return headers >= 2 ? (double)(hi - lo) / (double)headers : 400.0;
+}
+
+// GetNextEntry on a mapped FASTA text as a view -- the arithmetic of next_entry_plain(), or (f.gz_lines) of next_entry_gz(): the header line, the
+// first sequence line, the sequence's length, and whether it lies in more than that one line (fasta_join then makes it one string).
+// `f` is a cursor without a line index.
+struct FastaView {
+	const char *hdr = nullptr, *seq = nullptr;
+	int hdr_len = 0, rlen = 0;
+	bool joined = false;
+	size_t seq_pos = 0;           // where the first line behind the header starts
+};
+
+bool fasta_view_next(MappedFile &f, FastaView &v)
+{
+	const char *p;
+	ssize_t len = f.line(p);
+	if (len == -1) return false;
+	v = FastaView();
+	v.hdr = p; v.hdr_len = (int)len; v.seq_pos = f.pos;
+	if (f.gz_lines) {
+		if (header_view(p, (int)len).empty() || (p[0] != '@' && p[0] != '>')) return true;
+		ssize_t sl = f.line(p);
+		if (sl == -1) { p = v.hdr; sl = len; }            // (the buffer still holds the header line, next_entry_gz)
+		v.seq = p; v.rlen = std::max(0, (int)sl - 1);
+		return true;
+	}
+	int lines = 0;
+	for (;;) {
+		const size_t at = f.pos;
+		ssize_t sl = f.line(p);
+		if (sl == -1) break;
+		if (p[0] == '>') { f.pos = at; break; }
+		if (lines++ == 0) v.seq = p;
+		v.rlen += (int)sl - 1;
+	}
+	v.joined = lines > 1;
+	return true;
+}
+
+// the sequence lines of a record of a plain FASTA text, each without its last byte, one after the other (v.rlen bytes)
+void fasta_join(const char *data, size_t size, const FastaView &v, char *out)
+{
+	MappedFile f;
+	f.data = data; f.size = size; f.pos = v.seq_pos;
+	const char *p;
+	for (ssize_t sl; (sl = f.line(p)) != -1 && p[0] != '>'; out += sl - 1) memcpy(out, p, (size_t)(sl - 1));
 }
 
 // The records whose four lines all lie in the indexed window, as views -- the same arithmetic as view_next(), but for all

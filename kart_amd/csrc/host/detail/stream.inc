@@ -194,11 +194,55 @@ struct StreamBatch {
 	size_t text_begin[2] = {0, 0}, text_end[2] = {0, 0};   // the file bytes of the batch's windows (a growing text: nothing in front of text_begin is read once the batch is committed)
 };
 
+inline const char *f_data_of(const Source &src, int64_t r) { return (src.sep && (r & 1) ? src.m2 : src.m1).data; }
+
 // the reads of chunk `ck` listed in ck.hq, parsed from the mapped input exactly as view_next() / materialise() do
 void stream_own_reads(const Ctx &cx, const Source &src, const StreamBatch &b, ChunkState &ck)
 {
 	const size_t nh = ck.hq.size();
 	ck.own_reads.assign(nh, Read());
+	if (!cx.fastq) {
+		// FASTA: GetNextEntry from the record's header on (fasta_view_next).  A sequence of several lines, and a mate held reverse-complemented,
+		// need storage of their own: Read::seq is one piece of memory
+		std::vector<FastaView> views(nh);
+		std::vector<size_t> size_of(nh);
+		size_t own = 0;
+		for (size_t k = 0; k < nh; ++k) {
+			const int64_t r = ck.begin + ck.hq[k];
+			const int f = src.sep ? (int)(r & 1) : 0;
+			const int64_t j = src.sep ? r >> 1 : r;
+			const MappedFile &mf = f ? src.m2 : src.m1;
+			MappedFile one;
+			one.data = mf.data; one.size = size_of[k] = mf.grow ? b.text_end[f] : mf.map_size; one.pos = b.abs0[f] + (size_t)b.res.rec_start[f][j];
+			one.gz_lines = mf.gz_lines;
+			if (!fasta_view_next(one, views[k])) { fprintf(stderr, "Error! a record the device parsed cannot be read back\n"); exit(1); }
+			if (views[k].joined || (cx.opt.paired && (r & 1))) own += (size_t)views[k].rlen;
+		}
+		ck.own_chars.assign(own, '\0');
+		std::string joined;
+		size_t at = 0;
+		for (size_t k = 0; k < nh; ++k) {
+			const FastaView &v = views[k];
+			const int64_t r = ck.begin + ck.hq[k];
+			const bool flip = cx.opt.paired && (r & 1);
+			Read &rd = ck.own_reads[k];
+			rd.name = header_view(v.hdr, v.hdr_len);
+			rd.rlen = v.rlen;
+			if (!v.joined && !flip) { rd.seq = std::string_view(v.seq ? v.seq : "", (size_t)v.rlen); continue; }
+			char *dst = &ck.own_chars[at];
+			const char *seq = v.seq;
+			if (v.joined) {
+				char *to = dst;
+				if (flip) { joined.assign((size_t)v.rlen, '\0'); to = &joined[0]; }
+				fasta_join((f_data_of(src, r)), size_of[k], v, to);
+				seq = to;
+			}
+			if (flip) revcomp_into(dst, seq, (size_t)v.rlen);
+			rd.seq = std::string_view(dst, (size_t)v.rlen);
+			at += (size_t)v.rlen;
+		}
+		return;
+	}
 	size_t flipped = 0;
 	std::vector<RecView> views(nh);
 	for (size_t k = 0; k < nh; ++k) {
@@ -319,12 +363,12 @@ bool map_library_stream(Ctx &cx, Source &src, StreamBackend &sb, Writer *writer,
 	}
 	feed.target = std::max<int64_t>(chunk_limit, std::min<int64_t>(full_target, ramp_from));
 	for (int f = 0; f < nf; ++f) {
-		// bytes per record from the first records of the file (four lines each)
+		// bytes per record from the first records of the file (four lines each; FASTA: a header line each)
 		const MappedFile &mf = f ? src.m2 : src.m1;
 		size_t lo = feed.pos[f], hi = std::min(std::min(feed.end[f], mf.size), lo + ((size_t)1 << 18));
 		int64_t lines = 0, blank = 0;
 		count_lines(mf.data, lo, hi, lines, blank);
-		feed.bpr[f] = lines >= 8 ? 4.0 * (double)(hi - lo) / (double)lines : 400.0;
+		feed.bpr[f] = !cx.fastq ? fasta_bytes_per_record(mf.data, lo, hi) : lines >= 8 ? 4.0 * (double)(hi - lo) / (double)lines : 400.0;
 	}
 	// the SAM text of short reads is about 1.2 x the FASTQ text it comes from: its pages are allocated while the first batches map
 	if (writer && !held) {

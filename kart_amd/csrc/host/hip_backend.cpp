@@ -70,6 +70,10 @@ public:
 	{
 		if (kg_stream_set_format(s_, bam ? KG_STREAM_FORMAT_BAM : KG_STREAM_FORMAT_SAM) != KG_OK) die("kg_stream_set_format");
 	}
+	void set_input(bool fasta) override
+	{
+		if (kg_stream_set_input(s_, fasta ? KG_STREAM_INPUT_FASTA : KG_STREAM_INPUT_FASTQ) != KG_OK) die("kg_stream_set_input");
+	}
 	kg_stream *handle() const { return s_; }
 
 private:

@@ -225,7 +225,12 @@ int run_mapping(const Options &opt, const RefData &ref, KernelBackend &kern, FIL
 		if (sep && !in2.fp && !in2.gz) continue;
 		src.sep = sep;
 		src.fast = want_fast && src.m1.open(f1) && (!sep || src.m2.open(opt.files2[lib]));
-		src.gzfast = gz && cx.fastq && !getenv("KART_AMD_NO_MMAP");
+		// plain FASTA is mapped for the device stream alone (the getline() reader above continues wherever that one stops); gz of either format
+		// is inflated by the several-thread reader
+		src.fasta_fast = !gz && !cx.fastq && !getenv("KART_AMD_NO_MMAP") && src.m1.open(f1) && (!sep || src.m2.open(opt.files2[lib]));
+		// (gz FASTA: only where the stream will take the library -- pipeline.inc's conditions; otherwise gzgets() reads it as it always did)
+		const bool gz_fasta_stream = !cx.fastq && !opt.pacbio && !g_check_align && cx.kern.has_stream() && !getenv("KART_AMD_NO_GZ_STREAM") && !shard.active();
+		src.gzfast = gz && (cx.fastq || gz_fasta_stream) && !getenv("KART_AMD_NO_MMAP");
 		if (src.gzfast) {
 			src.g1.f = in1.gz; src.g2.f = in2.gz; gzbuffer(in1.gz, 1 << 20); if (in2.gz) gzbuffer(in2.gz, 1 << 20);
 			src.g1.path = f1; if (sep) src.g2.path = opt.files2[lib];

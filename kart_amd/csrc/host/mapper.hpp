@@ -72,7 +72,7 @@ struct NwJobs {
 	}
 };
 
-// FASTQ text in, SAM text or BAM records out (kg_stream_*, include/kart_amd.h): `lanes` batches in flight on the device, the host only moves
+// FASTQ or FASTA text in, SAM text or BAM records out (kg_stream_*, include/kart_amd.h): `lanes` batches in flight on the device, the host only moves
 // bytes.  The calls of one lane must not overlap; different lanes are driven from different threads.
 struct StreamBackend {
 	virtual ~StreamBackend() {}
@@ -93,6 +93,8 @@ struct StreamBackend {
 	virtual void group_absent(int lane, int rounds) { (void)lane; (void)rounds; }
 	// what map() leaves in the result's sam / sam_off from here on: SAM lines, or (bam) uncompressed BAM records (kg_stream_set_format); while no lane works
 	virtual void set_format(bool bam) { (void)bam; }
+	// what parse() takes the text for from here on: 4-line FASTQ, or (fasta) FASTA records (kg_stream_set_input); while no lane works
+	virtual void set_input(bool fasta) { (void)fasta; }
 };
 
 // The fragment pairs of one chunk whose alignment GenerateNormalPairAlignment (src/tools.cpp:142-223) is to produce -- 8-mer partition,

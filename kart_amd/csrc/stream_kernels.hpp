@@ -1,4 +1,4 @@
-// stream_kernels.hpp -- argument blocks of the FASTQ-text-in / SAM-text-out kernels (stream_kernels.hip) shared with the C ABI.
+// stream_kernels.hpp -- argument blocks of the FASTQ/FASTA-text-in / SAM-text-out kernels (stream_kernels.hip) shared with the C ABI.
 //
 // The reference parses its input one record at a time on the host (GetNextEntry / GetNextChunk, src/GetData.cpp:51-143) and prints
 // its output one record at a time (OutputPairedAlignments / OutputSingledAlignments, src/Mapping.cpp:177-315).  Here both ends run
@@ -22,6 +22,7 @@ enum {
 	FQM_NUL = 4,                         // a NUL byte somewhere in a window (the reference treats lines as C strings)
 	FQM_OVERFLOW = 5,                    // more lines than the line table holds
 	FQM_READS = 6, FQM_CHUNKS = 7, FQM_BASES = 8, FQM_USED0 = 9, FQM_USED1 = 10, FQM_STOP = 11, FQM_DONE = 12,
+	FQM_RECS0 = 13, FQM_RECS1 = 14,      // (FASTA) header lines = records begun in window 0 / 1
 	FQM_WORDS = 16
 };
 
@@ -39,6 +40,12 @@ struct FqWindow {
 	uint32_t *rec_qual;        // offset of the quality line
 	int32_t *rec_rlen;         // sequence line length - 1
 	int32_t *rec_qlen;         // min(quality line length, rlen)
+	// FASTA (kg_stream_set_input): a record is a header line and every line up to the next one that starts with '>'.  There rec_seq is the
+	// offset of the first sequence line, rec_qual that line's number, rec_qlen the number of sequence lines, rec_rlen the sum of (length - 1) over them
+	int64_t rec_capacity;      // entries of the rec_* arrays
+	uint64_t *line_acc;        // [line_capacity + 1] per line (header ? 1 : 0) << 32 | (header ? 0 : length - 1), then (in place) their exclusive scan:
+	                           //   line i belongs to record (acc[i + 1] >> 32) - 1, and (uint32_t)acc[i] sequence characters lie in front of it
+	uint32_t *rec_line;        // [rec_capacity + 1] the header line of every record, then the number of lines
 };
 
 struct FqArgs {
@@ -46,6 +53,7 @@ struct FqArgs {
 	int two_files;             // mates alternate between the windows (else every read comes from window 0)
 	int paired;                // the second read of every pair is held reverse-complemented (src/GetData.cpp:125-135)
 	int chunk_reads;           // ReadChunkSize (4000)
+	int fasta;                 // the text is FASTA (kg_stream_set_input): fa_* kernels make the record table
 	int gz_lines;              // the text comes out of a gz file: records that gzgets() with its 1000-byte buffer reads differently end the batch (kg_stream_window)
 	int64_t max_reads;         // capacity of the batch (a multiple of chunk_reads)
 	int64_t want_reads;        // take at most this many (a multiple of chunk_reads, <= max_reads)
@@ -60,6 +68,7 @@ struct FqArgs {
 struct SamArgs {
 	FqWindow w[2];
 	int two_files, paired;
+	int fasta;                       // the reads have no qualities: the column is "*" (src/Mapping.cpp:186,218,234,259,280,303)
 	const uint8_t *enc;
 	const int64_t *read_off;
 	int64_t n_reads;
@@ -75,6 +84,7 @@ struct SamArgs {
 };
 
 size_t fq_scan_temp_bytes(int64_t max_items);
+size_t fa_scan_temp_bytes(int64_t max_lines);      // the scan over FqWindow::line_acc
 // line index + record table of both windows, read lengths and their scan, the plan (meta)
 hipError_t launch_fq_parse(const FqArgs &a, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream);
 hipError_t launch_fq_materialise(const FqArgs &a, int n_cu, hipStream_t stream);
