@@ -38,6 +38,15 @@ KG_OP_DIAG, KG_OP_GAP1, KG_OP_GAP2 = 0, 1, 2
 
 SEED_DT = np.dtype([("gPos", "<i8"), ("rPos", "<i4"), ("len", "<i4")])
 CAND_DT = np.dtype([("posDiff", "<i8"), ("score", "<i4"), ("count", "<i4"), ("first", "<i8")])
+KG_ALN_NONE, KG_ALN_UNMAPPED, KG_ALN_MAPPED, KG_ALN_HOST = 0, 1, 2, 3
+KG_ALN_CIGAR_MAX = 48
+# kg_aln_record and kg_chunk_stats (include/kart_amd.h), field for field
+ALN_DT = np.dtype([("pos", "<i8"), ("mate_pos", "<i8"), ("kind", "<i4"), ("flag", "<i4"), ("chr", "<i4"), ("mapq", "<i4"), ("tlen", "<i4"),
+                   ("score", "<i4"), ("sub_score", "<i4"), ("est_lo", "<i4"), ("est_hi", "<i4"), ("has_mate", "u1"), ("flip", "u1"), ("cigar_len", "u1"),
+                   ("rescue", "u1"), ("cigar", "S%d" % KG_ALN_CIGAR_MAX), ("next", "<i4"), ("primary", "u1"), ("pad", "u1", (3,))])
+CHUNK_STATS_DT = np.dtype([("paired", "<i8"), ("distance", "<i8"), ("lo", "<i8"), ("hi", "<i8"), ("unmapped", "<i4"), ("unique", "<i4"),
+                           ("host_pairs", "<i4"), ("rescue_wanted", "<i4")])
+assert ALN_DT.itemsize == 112 and CHUNK_STATS_DT.itemsize == 48
 
 # every symbol include/kart_amd.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
@@ -195,6 +204,8 @@ def load_library() -> C.CDLL:
                                        C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.kg_candidates_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                                       C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    L.kg_align_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]
+    L.kg_align_reasons.argtypes = [C.c_void_p, C.c_void_p]
     L.kg_nw_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.kg_nw_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p]
@@ -317,6 +328,47 @@ class Workspace:
                 lst.append((int(c["score"]), int(c["posDiff"]), cseeds[c["first"]:c["first"] + c["count"]].copy()))
             at += int(ncand[r])
             out.append(lst)
+        return out
+
+    def align_batch(self, chunk_off, chunk_paired, est_distance: int = 1500, max_insert: int = 1500, max_gaps: int = 5, multi_hit: bool = False,
+                    unset_flag: int = 0):
+        """kg_align_batch for the batch the last seed_batch() (KG_INPUT_ASCII: the report reads the characters) + candidates_batch() calls left
+        on the device: chunk_off[n_chunks + 1] read ranges, chunk_paired[n_chunks] (pairs (2q, 2q + 1), mate 2 held reverse-complemented).
+        Returns (records, chunk_stats): ALN_DT / CHUNK_STATS_DT arrays.  records[:n_reads] are the reads' own; with multi_hit the further
+        records of a read follow behind them, chained through `next` (an index into the same array, -1 at the end)."""
+        chunk_off = np.ascontiguousarray(chunk_off, dtype=np.int64)
+        chunk_paired = np.ascontiguousarray(chunk_paired, dtype=np.uint8)
+        n_chunks = len(chunk_paired)
+        if len(chunk_off) != n_chunks + 1:
+            raise KartAmdError("align_batch: chunk_off must hold one entry more than chunk_paired")
+        stats = np.zeros(n_chunks, dtype=CHUNK_STATS_DT)
+        out = C.c_void_p()
+        _check(self.lib.kg_align_batch(self.h, _ptr(chunk_off), _ptr(chunk_paired), n_chunks, est_distance, max_insert, max_gaps, 1 if multi_hit else 0,
+                                       unset_flag, C.byref(out), _ptr(stats)), "kg_align_batch")
+        n = int(chunk_off[n_chunks])
+
+        def view(count):
+            return np.frombuffer((C.c_char * (count * ALN_DT.itemsize)).from_address(out.value), dtype=ALN_DT)
+
+        # ASSUMES, of the kernels as they stand (the C interface promises n_reads records and returns no count of the chained ones): the
+        # kernels set `next` (-1, or the slot of the next record) in every record of kind NONE, UNMAPPED and MAPPED, the per-read ones and
+        # the chained ones alike; a link points at a slot >= n_reads of the same library-owned array, which the library has copied to the
+        # host up to the last slot in use.  The memory behind records[n_reads - 1] is read on that trust: should the library stop copying
+        # the chained records, or leave a `next` unset, this loop is what has to change (or the interface has to return the count).
+        count = n
+        while multi_hit and count:          # the library does not return how many chained records it made: follow the links it did make
+            v = view(count)                 # (a record handed back, KG_ALN_HOST, carries no link: its `next` is whatever the slot held)
+            links = v["next"][v["kind"] != KG_ALN_HOST]
+            reach = int(links.max()) + 1 if len(links) else 0
+            if reach <= count:
+                break
+            count = reach
+        return (view(count).copy() if count else np.zeros(0, ALN_DT)), stats
+
+    def align_reasons(self) -> np.ndarray:
+        """kg_align_reasons: running tallies of why read pairs came back as KG_ALN_HOST (uint64[16], see include/kart_amd.h)"""
+        out = np.zeros(16, dtype=np.uint64)
+        _check(self.lib.kg_align_reasons(self.h, _ptr(out)), "kg_align_reasons")
         return out
 
     def seed_batch_device(self, d_enc, d_offsets, n_reads, n_bases, d_seed_offsets, d_seeds, seed_capacity, mode,
