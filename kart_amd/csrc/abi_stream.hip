@@ -19,6 +19,20 @@
 
 namespace {
 
+// the words of a lane's page-locked scratch behind the parser's (Lane::h_meta + FQM_WORDS)
+enum LaneWord {
+	LW_TEXT_BYTES = 0,                                 // kg_stream_map: bytes of the batch's text
+	LW_HOST_READS = 1,                                 // reads handed back
+	LW_FORMAT_ERRORS = 2,                              // records formatted to a size other than the one announced
+	LW_EXTRA_RECORDS = 3,                              // extra records of -m
+	LW_ALN_COUNTS = 8,                                 // [8, 16) kg_stream_timing_t::aln_counts of the batch: the alignment stage's seven list sizes, of which ...
+	LW_ALN_TRIVIAL = 14,                               // ... the last (the piece count, which nobody reads) gives way to the pairs aln_trivial_kernel decided,
+	LW_ALN_GENERAL = 15,                               // and the candidates its fast plan kernel left to the general one
+	LW_CHECKSUM = 16,                                  // [16, 18) sam_checksum_kernel's sums (KG_STREAM_CHECKSUM)
+	LW_FETCH_SEEDS = 18,                               // [18, 20) kg_stream_fetch: the candidate seeds' offsets at either end of the reads asked for
+	LW_WORDS = 24
+};
+
 struct Lane {
 	kg_workspace *ws = nullptr;
 	// device
@@ -39,7 +53,7 @@ struct Lane {
 	int64_t d_sam_capacity = 0;
 	// page-locked
 	char *h_text[2] = {nullptr, nullptr};
-	int64_t *h_meta = nullptr;                         // [FQM_WORDS] + [24] spare words for totals
+	int64_t *h_meta = nullptr;                         // [FQM_WORDS] the parser's plan + [LW_WORDS] what the batch's small copies land in (LaneWord)
 	char *h_sam = nullptr;
 	int64_t h_sam_capacity = 0;
 	int64_t *h_sam_off = nullptr, *h_cand_off = nullptr;
@@ -191,6 +205,60 @@ int64_t out_capacity(const kg_stream_config &cfg, int format)
 	return 2 * cfg.max_window + (format == KG_STREAM_FORMAT_BAM ? 144 : 64) * cfg.max_reads + 4096;
 }
 
+// A buffer that has to hold more: a new one of `bytes` in its place (nobody needs what the old one holds).  The caller synchronises the lane's
+// stream first where the device may still use the old one, and keeps the capacity beside it.  kAllocFirst: the old buffer stays until the new one
+// exists, so that a failure leaves it usable.
+enum GrowOrder { kFreeFirst, kAllocFirst };
+template <class T> hipError_t grow_device(T *&p, size_t bytes, GrowOrder order = kFreeFirst)
+{
+	T *old = p;
+	if (order == kFreeFirst) {
+		if (old) { hipError_t e = hipFree(old); if (e != hipSuccess) return e; }
+		p = old = nullptr;
+	}
+	T *fresh = nullptr;
+	hipError_t e = hipMalloc((void **)&fresh, bytes);
+	if (e != hipSuccess) return e;
+	if (old) (void)hipFree(old);
+	p = fresh;
+	return hipSuccess;
+}
+template <class T> hipError_t grow_pinned(T *&p, size_t bytes)
+{
+	if (p) { hipError_t e = hipHostFree(p); if (e != hipSuccess) return e; }
+	p = nullptr;
+	return hipHostMalloc((void **)&p, bytes, hipHostMallocDefault);
+}
+
+// what a search launch over `reads` reads fetched, from the kernel's own counters `c` (those kg_workspace_traffic exports)
+double search_useful_bytes(const kg_index *ix, const unsigned long long *c, int64_t reads)
+{
+	const double sa_bytes = ix->view.fsa32 ? 4.0 : 8.0;
+	return 8.0 * (double)c[17] + 32.0 * (double)c[18] + (double)c[25] + sa_bytes * (double)c[8] + 48.0 * (double)c[20] + 8.0 * (double)c[21] + 20.0 * (double)reads + 32.0 * (double)c[1];
+}
+
+// ... with the capacity kept beside the buffer: unchanged while the old buffer is still there, zero while there is none
+template <class T, class C> hipError_t grow_device(T *&p, C &capacity, C want, size_t bytes)
+{
+	hipError_t e = grow_device(p, bytes);
+	capacity = e == hipSuccess ? want : p ? capacity : 0;
+	return e;
+}
+template <class T, class C> hipError_t grow_pinned(T *&p, C &capacity, C want, size_t bytes)
+{
+	hipError_t e = grow_pinned(p, bytes);
+	capacity = e == hipSuccess ? want : p ? capacity : 0;
+	return e;
+}
+
+// (sg.mu held) every lane of the group has arrived with a batch or sits the round out
+bool round_complete(const SeedGroup &sg)
+{
+	int accounted = sg.arrived;
+	for (int i = 0; i < sg.size; ++i) accounted += (!sg.present[i] && sg.absent_rounds[i] != 0) ? 1 : 0;
+	return accounted >= sg.size;
+}
+
 float elapsed(hipEvent_t a, hipEvent_t b)
 {
 	float ms = 0;
@@ -290,7 +358,7 @@ int kg_stream_open(kg_index *ix, const kg_stream_config *cfg, kg_stream **out)
 		HIP_TRY(hipMalloc((void **)&l.d_host_list, 4 * (size_t)(n + 8)));
 		HIP_TRY(hipMalloc((void **)&l.d_sam_off, 8 * (size_t)(n + 8)));
 		HIP_TRY(hipMalloc((void **)&l.d_sam_ctl, 8 * 4));
-		HIP_TRY(hipHostMalloc((void **)&l.h_meta, 8 * (FQM_WORDS + 24), hipHostMallocDefault));
+		HIP_TRY(hipHostMalloc((void **)&l.h_meta, 8 * (FQM_WORDS + LW_WORDS), hipHostMallocDefault));
 		HIP_TRY(hipHostMalloc((void **)&l.h_sam_off, 8 * (size_t)(n + 8), hipHostMallocDefault));
 		HIP_TRY(hipHostMalloc((void **)&l.h_cand_off, 8 * (size_t)(n + 8), hipHostMallocDefault));
 		HIP_TRY(hipHostMalloc((void **)&l.h_host_list, 4 * (size_t)(n + 8), hipHostMallocDefault));
@@ -333,15 +401,11 @@ int kg_stream_set_format(kg_stream *s, int format)
 	for (Lane &l : s->lanes) {
 		if (l.d_sam_capacity < want) {
 			HIP_TRY(hipStreamSynchronize(l.ws->stream));
-			HIP_TRY(hipFree(l.d_sam)); l.d_sam = nullptr; l.d_sam_capacity = 0;
-			HIP_TRY(hipMalloc((void **)&l.d_sam, (size_t)want));
-			l.d_sam_capacity = want;
+			HIP_TRY(grow_device(l.d_sam, l.d_sam_capacity, want, (size_t)want));
 		}
 		if (l.h_sam_capacity < want) {
 			HIP_TRY(hipStreamSynchronize(l.ws->stream));
-			HIP_TRY(hipHostFree(l.h_sam)); l.h_sam = nullptr; l.h_sam_capacity = 0;
-			HIP_TRY(hipHostMalloc((void **)&l.h_sam, (size_t)want, hipHostMallocDefault));
-			l.h_sam_capacity = want;
+			HIP_TRY(grow_pinned(l.h_sam, l.h_sam_capacity, want, (size_t)want));
 		}
 	}
 	s->format = format;
@@ -363,10 +427,7 @@ int kg_stream_set_input(kg_stream *s, int input)
 			if (s->fasta_sized) break;
 			HIP_TRY(hipStreamSynchronize(l.ws->stream));
 			for (int f = 0; f < 2; ++f) {
-				uint32_t *wider = nullptr;                 // (the old table stays until the new one exists: a failure leaves the stream usable for FASTQ)
-				HIP_TRY(hipMalloc((void **)&wider, 4 * 6 * (size_t)rec_capacity));
-				(void)hipFree(l.d_rec[f]);
-				l.d_rec[f] = wider;
+				HIP_TRY(grow_device(l.d_rec[f], 4 * 6 * (size_t)rec_capacity, kAllocFirst));     // (a failure leaves the stream usable for FASTQ)
 				if (!l.d_line_acc[f]) HIP_TRY(hipMalloc((void **)&l.d_line_acc[f], 8 * (size_t)(s->line_capacity + 1)));
 				if (!l.d_rec_line[f]) HIP_TRY(hipMalloc((void **)&l.d_rec_line[f], 4 * (size_t)(rec_capacity + 1)));
 				HIP_TRY(hipMemset(l.d_line_acc[f], 0, 8 * (size_t)(s->line_capacity + 1)));
@@ -374,9 +435,7 @@ int kg_stream_set_input(kg_stream *s, int input)
 			}
 			if (l.scan_bytes < want_scan) {
 				HIP_TRY(hipStreamSynchronize(l.ws->stream));
-				HIP_TRY(hipFree(l.d_scan)); l.d_scan = nullptr; l.scan_bytes = 0;
-				HIP_TRY(hipMalloc(&l.d_scan, want_scan));
-				l.scan_bytes = want_scan;
+				HIP_TRY(grow_device(l.d_scan, l.scan_bytes, want_scan, want_scan));
 			}
 		}
 	}
@@ -488,11 +547,6 @@ static int group_seed(kg_stream *s, int lane, int64_t n, int64_t n_bases, int64_
 	sg.present[j] = true;
 	sg.n_reads[j] = n;
 	sg.arrived++;
-	auto complete = [&]() {
-		int accounted = sg.arrived;
-		for (int i = 0; i < sg.size; ++i) accounted += (!sg.present[i] && sg.absent_rounds[i] != 0) ? 1 : 0;
-		return accounted >= sg.size;
-	};
 	auto run_round = [&]() {           // (sg.mu held by the caller; every other lane of the group waits or is absent)
 		kg_workspace *gw = sg.ws;
 		int64_t counts[kMaxSeedSegments];
@@ -530,16 +584,13 @@ static int group_seed(kg_stream *s, int lane, int64_t n, int64_t n_bases, int64_
 	for (;;) {
 		if (sg.aborted) { leave(); return fail(KG_ERR_ARG, "kg_stream_map: the stream's seeding groups were aborted"); }
 		if (sg.round != my_round) break;
-		if (complete()) {
+		if (round_complete(sg)) {
 			run_round();
 			*was_leader = true;
 			if (sg.rc == KG_OK) {
 				kg_workspace *gw = sg.ws;
 				*search_ms = gw->profiling && gw->ev[0] ? elapsed(gw->ev[0], gw->ev[1]) : 0;
-				const unsigned long long *c = sg.h_ctl;
-				const double sa_bytes = s->ix->view.fsa32 ? 4.0 : 8.0;
-				const int64_t reads = gw->group_prefix[sg.size];
-				*useful_bytes = 8.0 * (double)c[17] + 32.0 * (double)c[18] + (double)c[25] + sa_bytes * (double)c[8] + 48.0 * (double)c[20] + 8.0 * (double)c[21] + 20.0 * (double)reads + 32.0 * (double)c[1];
+				*useful_bytes = search_useful_bytes(s->ix, sg.h_ctl, gw->group_prefix[sg.size]);
 			}
 			break;
 		}
@@ -570,29 +621,31 @@ static int group_seed(kg_stream *s, int lane, int64_t n, int64_t n_bases, int64_
 	return KG_OK;
 }
 
-int kg_stream_map(kg_stream *s, int lane, const kg_stream_params *prm, kg_stream_result *out)
-{
-	if (!s || !prm || !out || lane < 0 || lane >= (int)s->lanes.size()) return fail(KG_ERR_ARG, "kg_stream_map: bad argument");
-	Lane &l = s->lanes[(size_t)lane];
-	if (!l.have_batch) return fail(KG_ERR_ARG, "kg_stream_map: no parsed batch in lane %d (kg_stream_parse first)", lane);
-	memset(out, 0, sizeof(*out));
-	kg_index *ix = s->ix;
-	kg_workspace *ws = l.ws;
-	hipStream_t st = ws->stream;
-	HIP_TRY(hipSetDevice(ix->device));
-	KtUse kt_use(ws->profiling ? &ws->kt : nullptr);
-	const int64_t n = l.parsed.n_reads;
-	const int n_chunks = (int)l.parsed.n_chunks;
-	// ---- seeding (IdentifySeedPairs_FastMode) and chaining on the resident characters ---------------------------------------
-	int64_t n_seeds = 0, totals[2] = {0, 0};
-	const bool grouped = !s->groups.empty();
-	bool group_leader = false;
+// ---- kg_stream_map, piece by piece: all on the lane's stream, in this order --------------------------------------------------------
+
+// what one kg_stream_map call carries from piece to piece
+struct MapCall {
+	const kg_stream_params *prm = nullptr;
+	int64_t n = 0;                                     // reads of the batch
+	int n_chunks = 0;
+	bool grouped = false, group_leader = false;        // group_leader: this call launched its group's round (the launch counts once in the statistics)
 	float group_search_ms = 0;
 	double group_useful = 0;
+	int64_t n_seeds = 0, totals[2] = {0, 0};           // candidates and their seeds
+	AlnArgs a;
+	SamArgs q;
+	bool checksum = false;
+	int64_t sam_bytes = 0, n_host = 0, extra = 0;      // bytes of text, reads handed back, extra records of -m
+};
+
+// seeding (IdentifySeedPairs_FastMode) on the resident characters: in the lane's group's round, after which the lane takes its turn, or alone
+static int map_seed(kg_stream *s, int lane, MapCall &m, GroupTurn &turn)
+{
+	Lane &l = s->lanes[(size_t)lane];
+	kg_workspace *ws = l.ws;
 	int rc;
-	GroupTurn turn;
-	if (grouped) {
-		rc = group_seed(s, lane, n, l.parsed.n_bases, &n_seeds, &group_leader, &group_search_ms, &group_useful);
+	if (m.grouped) {
+		rc = group_seed(s, lane, m.n, l.parsed.n_bases, &m.n_seeds, &m.group_leader, &m.group_search_ms, &m.group_useful);
 		static const bool no_turns = getenv("KG_GROUP_NO_TURNS") != nullptr;          // A/B aid: the lanes of a group start their stages at once
 		SeedGroup &sg = *s->groups[(size_t)lane / (size_t)s->cfg.seed_group];
 		if (rc == KG_OK && !no_turns && !turn.acquire(sg, lane - sg.first)) rc = fail(KG_ERR_ARG, "kg_stream_map: the stream's seeding groups were aborted");
@@ -601,141 +654,200 @@ int kg_stream_map(kg_stream *s, int lane, const kg_stream_params *prm, kg_stream
 			sg.aborted = true;
 			sg.cv.notify_all();
 		}
-	} else rc = kgi_seed_resident(ws, KG_MODE_FAST | KG_INPUT_ASCII, s->min_seed_len, KG_OCC_THR_DEFAULT, n, l.parsed.n_bases, &n_seeds);
+	} else rc = kgi_seed_resident(ws, KG_MODE_FAST | KG_INPUT_ASCII, s->min_seed_len, KG_OCC_THR_DEFAULT, m.n, l.parsed.n_bases, &m.n_seeds);
 	if (rc != KG_OK) return rc;
-	if (!grouped) HIP_TRY(hipMemcpyAsync(l.h_ctl, ws->d_ctl, 8 * kCtlWords, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipEventRecord(l.ev[2], st));
-	rc = kgi_chain_resident(ws, 0, prm->max_gaps, totals);
+	if (!m.grouped) HIP_TRY(hipMemcpyAsync(l.h_ctl, ws->d_ctl, 8 * kCtlWords, hipMemcpyDeviceToHost, ws->stream));
+	HIP_TRY(hipEventRecord(l.ev[2], ws->stream));
+	return KG_OK;
+}
+
+static int map_chain(Lane &l, MapCall &m)
+{
+	int rc = kgi_chain_resident(l.ws, 0, m.prm->max_gaps, m.totals);
 	if (rc != KG_OK) return rc;
-	HIP_TRY(hipEventRecord(l.ev[3], st));
-	// ---- the per-read report ------------------------------------------------------------------------------------------------
+	HIP_TRY(hipEventRecord(l.ev[3], l.ws->stream));
+	return KG_OK;
+}
+
+// the per-read report
+static int map_report(Lane &l, MapCall &m)
+{
+	const int n_chunks = m.n_chunks;
 	std::vector<int64_t> chunk_off((size_t)n_chunks + 1);
 	std::vector<uint8_t> chunk_paired((size_t)n_chunks, (uint8_t)(l.win.paired ? 1 : 0));
-	for (int c = 0; c <= n_chunks; ++c) chunk_off[(size_t)c] = std::min<int64_t>(n, (int64_t)c * l.win.chunk_reads);
+	for (int c = 0; c <= n_chunks; ++c) chunk_off[(size_t)c] = std::min<int64_t>(m.n, (int64_t)c * l.win.chunk_reads);
 	if (n_chunks > l.chunk_capacity) {
-		if (l.h_chunk_stats) HIP_TRY(hipHostFree(l.h_chunk_stats));
-		l.h_chunk_stats = nullptr;
-		l.chunk_capacity = n_chunks + n_chunks / 2 + 64;
-		HIP_TRY(hipHostMalloc((void **)&l.h_chunk_stats, sizeof(kg_chunk_stats) * (size_t)l.chunk_capacity, hipHostMallocDefault));
+		const int64_t want = n_chunks + n_chunks / 2 + 64;
+		HIP_TRY(grow_pinned(l.h_chunk_stats, l.chunk_capacity, want, sizeof(kg_chunk_stats) * (size_t)want));
 	}
-	AlnArgs a;
-	rc = kgi_align_resident(ws, chunk_off.data(), chunk_paired.data(), n_chunks, prm->est_distance, prm->max_insert, prm->max_gaps, prm->multi_hit,
-	                        prm->unset_flag, l.record_capacity, a);
+	int rc = kgi_align_resident(l.ws, chunk_off.data(), chunk_paired.data(), n_chunks, m.prm->est_distance, m.prm->max_insert, m.prm->max_gaps, m.prm->multi_hit,
+	                            m.prm->unset_flag, l.record_capacity, m.a);
 	if (rc != KG_OK) return rc;
-	HIP_TRY(hipEventRecord(l.ev[4], st));
-	// ---- the text -----------------------------------------------------------------------------------------------------------
-	SamArgs q;
+	HIP_TRY(hipEventRecord(l.ev[4], l.ws->stream));
+	return KG_OK;
+}
+
+// the size of every read's text (one sync: the totals come over), and buffers that hold the text and, on the host, the batch's candidates
+static int map_size_text(kg_stream *s, Lane &l, MapCall &m)
+{
+	kg_workspace *ws = l.ws;
+	hipStream_t st = ws->stream;
+	const int64_t n = m.n;
+	SamArgs &q = m.q;
 	q.w[0] = window_of(s, l, 0); q.w[1] = window_of(s, l, 1);
 	q.two_files = l.win.two_files ? 1 : 0; q.paired = l.win.paired ? 1 : 0;
 	q.fasta = l.fasta ? 1 : 0;
 	q.enc = ws->d_enc; q.read_off = ws->d_read_off; q.n_reads = n;
-	q.records = a.records;
+	q.records = m.a.records;
 	q.chr_names = s->d_chr_names; q.chr_name_off = s->d_chr_name_off;
 	q.sam_len = l.d_sam_len; q.sam_off = l.d_sam_off; q.sam = l.d_sam; q.sam_capacity = l.d_sam_capacity;
 	q.host_list = l.d_host_list; q.ctl = l.d_sam_ctl;
-	const bool bam = s->format == KG_STREAM_FORMAT_BAM;
-	HIP_TRY(bam ? launch_bam_size(q, l.d_scan, l.scan_bytes, ix->n_cu, st) : launch_sam_size(q, l.d_scan, l.scan_bytes, ix->n_cu, st));
-	int64_t *tot = l.h_meta + FQM_WORDS;              // [0] text bytes, [1] reads handed back, [2] format errors, [3] extra records of -m
-	HIP_TRY(hipMemcpyAsync(&tot[0], l.d_sam_off + n, 8, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(&tot[1], l.d_sam_ctl, 8, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(&tot[3], ws->d_aln_ctl + 7, 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(launch_text_size(q, s->format == KG_STREAM_FORMAT_BAM, l.d_scan, l.scan_bytes, s->ix->n_cu, st));
+	int64_t *word = l.h_meta + FQM_WORDS;
+	HIP_TRY(hipMemcpyAsync(&word[LW_TEXT_BYTES], l.d_sam_off + n, 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(&word[LW_HOST_READS], l.d_sam_ctl, 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(&word[LW_EXTRA_RECORDS], ws->d_aln_ctl + 7, 8, hipMemcpyDeviceToHost, st));
 	HIP_TRY(kgi_sync(ws));
-	const int64_t sam_bytes = tot[0], n_host = tot[1];
-	const int64_t extra = prm->multi_hit ? std::min<int64_t>(tot[3], a.extra_capacity) : 0;
+	const int64_t sam_bytes = m.sam_bytes = word[LW_TEXT_BYTES];
+	m.n_host = word[LW_HOST_READS];
+	m.extra = m.prm->multi_hit ? std::min<int64_t>(word[LW_EXTRA_RECORDS], m.a.extra_capacity) : 0;
 	if (sam_bytes > l.d_sam_capacity) {
 		// (never seen: the estimate in kg_stream_open is generous; -m on a repeat-rich genome could get here)
-		HIP_TRY(hipFree(l.d_sam)); l.d_sam = nullptr;
-		l.d_sam_capacity = sam_bytes + sam_bytes / 4;
-		HIP_TRY(hipMalloc((void **)&l.d_sam, (size_t)l.d_sam_capacity));
+		HIP_TRY(grow_device(l.d_sam, l.d_sam_capacity, sam_bytes + sam_bytes / 4, (size_t)(sam_bytes + sam_bytes / 4)));
 		q.sam = l.d_sam; q.sam_capacity = l.d_sam_capacity;
 	}
 	if (sam_bytes > l.h_sam_capacity) {
-		HIP_TRY(hipHostFree(l.h_sam)); l.h_sam = nullptr;
-		l.h_sam_capacity = sam_bytes + sam_bytes / 4;
-		HIP_TRY(hipHostMalloc((void **)&l.h_sam, (size_t)l.h_sam_capacity, hipHostMallocDefault));
+		HIP_TRY(grow_pinned(l.h_sam, l.h_sam_capacity, sam_bytes + sam_bytes / 4, (size_t)(sam_bytes + sam_bytes / 4)));
 	}
-	const int64_t cand_need = std::max(totals[0], totals[1]);
+	const int64_t cand_need = std::max(m.totals[0], m.totals[1]);
 	if (cand_need > l.h_cand_capacity) {
+		// (two buffers under one capacity: both are freed before either is allocated)
+		const int64_t want = std::max<int64_t>(cand_need + cand_need / 4 + 1024, 3 * s->cfg.max_reads);
 		if (l.h_cands) HIP_TRY(hipHostFree(l.h_cands));
 		if (l.h_cand_seeds) HIP_TRY(hipHostFree(l.h_cand_seeds));
 		l.h_cands = nullptr; l.h_cand_seeds = nullptr;
-		l.h_cand_capacity = std::max<int64_t>(cand_need + cand_need / 4 + 1024, 3 * s->cfg.max_reads);
-		HIP_TRY(hipHostMalloc((void **)&l.h_cands, sizeof(kg_candidate) * (size_t)l.h_cand_capacity, hipHostMallocDefault));
-		HIP_TRY(hipHostMalloc((void **)&l.h_cand_seeds, sizeof(kg_seed) * (size_t)l.h_cand_capacity, hipHostMallocDefault));
+		l.h_cand_capacity = 0;
+		HIP_TRY(grow_pinned(l.h_cands, sizeof(kg_candidate) * (size_t)want));
+		HIP_TRY(grow_pinned(l.h_cand_seeds, sizeof(kg_seed) * (size_t)want));
+		l.h_cand_capacity = want;
 	}
-	HIP_TRY(bam ? launch_bam_format(q, ix->n_cu, st) : launch_sam_format(q, ix->n_cu, st));
+	return KG_OK;
+}
+
+static int map_format(kg_stream *s, Lane &l, MapCall &m)
+{
+	hipStream_t st = l.ws->stream;
+	HIP_TRY(launch_text_format(m.q, s->format == KG_STREAM_FORMAT_BAM, s->ix->n_cu, st));
 	// measurement aid (bench.py's gpu_pipeline leg): the text summed on the device, for runs that never copy it into file pages (read per call: a session switches it on and off)
-	const bool checksum = getenv("KG_STREAM_CHECKSUM") != nullptr;
-	if (checksum) HIP_TRY(launch_sam_checksum(q, ix->n_cu, st));
+	m.checksum = getenv("KG_STREAM_CHECKSUM") != nullptr;
+	if (m.checksum) HIP_TRY(launch_sam_checksum(m.q, s->ix->n_cu, st));
 	HIP_TRY(hipEventRecord(l.ev[5], st));
-	// (grouped seeding) the turn is kept until the batch is back on the host.  Passing it on here -- so that this lane's copies overlap the
-	// next lane's kernels, KG_GROUP_TURN_EARLY=1 -- gives the same FASTQ -> SAM rate at 100 M reads (29.4-29.9 M against 29.8-30.4 M
-	// mapped reads/s) while the next lane's first kernel then waits behind this one's copies: chain_kernel 5.0 ms per launch instead of 0.35,
-	// the stage sums twice as long (profiles/r04u_trace_chain.log, r04v_ab_turn_late.log); the other group's lanes overlap either way.
-	static const bool turn_early = getenv("KG_GROUP_TURN_EARLY") != nullptr;
-	if (turn_early) turn.release();
-	if (sam_bytes > 0) HIP_TRY(hipMemcpyAsync(l.h_sam, l.d_sam, (size_t)sam_bytes, hipMemcpyDeviceToHost, st));
+	return KG_OK;
+}
+
+// the batch back on the host (the second sync) and described in *out
+static int map_copy_out(Lane &l, MapCall &m, kg_stream_result *out)
+{
+	kg_workspace *ws = l.ws;
+	hipStream_t st = ws->stream;
+	const int64_t n = m.n, n_host = m.n_host, extra = m.extra, *totals = m.totals;
+	const AlnArgs &a = m.a;
+	int64_t *word = l.h_meta + FQM_WORDS;
+	if (m.sam_bytes > 0) HIP_TRY(hipMemcpyAsync(l.h_sam, l.d_sam, (size_t)m.sam_bytes, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(l.h_sam_off, l.d_sam_off, 8 * (size_t)(n + 1), hipMemcpyDeviceToHost, st));
 	// the records, candidate offsets, candidates and their seeds stay on the device unless the caller wants them all: it asks for the chunks it needs
 	// (kg_stream_fetch) -- 207 of the 605 bytes per read that used to cross the link
-	const bool all = prm->fetch_all != 0;
+	const bool all = m.prm->fetch_all != 0;
 	l.mapped_reads = n; l.d_records = a.records;
 	if (all) HIP_TRY(hipMemcpyAsync(l.h_records, a.records, sizeof(kg_aln_record) * (size_t)(n + extra), hipMemcpyDeviceToHost, st));
 	else if (extra > 0) HIP_TRY(hipMemcpyAsync(l.h_records + n, a.records + n, sizeof(kg_aln_record) * (size_t)extra, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(l.h_chunk_stats, ws->d_chunk_stats, sizeof(kg_chunk_stats) * (size_t)n_chunks, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(l.h_chunk_stats, ws->d_chunk_stats, sizeof(kg_chunk_stats) * (size_t)m.n_chunks, hipMemcpyDeviceToHost, st));
 	if (all) HIP_TRY(hipMemcpyAsync(l.h_cand_off, ws->d_cand_off, 8 * (size_t)(n + 1), hipMemcpyDeviceToHost, st));
 	// the candidates travel with every batch: the reads handed back need them, and so does a pair the caller maps again because its
 	// speculated EstDistance did not hold
 	if (n_host > 0) HIP_TRY(hipMemcpyAsync(l.h_host_list, l.d_host_list, 4 * (size_t)n_host, hipMemcpyDeviceToHost, st));
 	if (all && totals[0] > 0) HIP_TRY(hipMemcpyAsync(l.h_cands, ws->d_dense_cands, sizeof(kg_candidate) * (size_t)totals[0], hipMemcpyDeviceToHost, st));
 	if (all && totals[1] > 0) HIP_TRY(hipMemcpyAsync(l.h_cand_seeds, ws->d_dense_seeds, sizeof(kg_seed) * (size_t)totals[1], hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(&tot[2], l.d_sam_ctl + 1, 8, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(&tot[8], ws->d_aln_ctl, 8 * 7, hipMemcpyDeviceToHost, st));          // the alignment stage's list sizes of this batch ...
-	HIP_TRY(hipMemcpyAsync(&tot[15], ws->d_aln_ctl + 32, 8, hipMemcpyDeviceToHost, st));        // ... and the candidates its fast plan kernel left to the general one
-	tot[16] = tot[17] = 0;
-	if (checksum) HIP_TRY(hipMemcpyAsync(&tot[16], l.d_sam_ctl + 2, 16, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(&tot[14], ws->d_aln_ctl + 36, 8, hipMemcpyDeviceToHost, st));        // ... and the pairs aln_trivial_kernel decided (in the place of the piece count, which nobody reads)
+	HIP_TRY(hipMemcpyAsync(&word[LW_FORMAT_ERRORS], l.d_sam_ctl + 1, 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(&word[LW_ALN_COUNTS], ws->d_aln_ctl, 8 * 7, hipMemcpyDeviceToHost, st));          // the alignment stage's list sizes of this batch ...
+	HIP_TRY(hipMemcpyAsync(&word[LW_ALN_GENERAL], ws->d_aln_ctl + 32, 8, hipMemcpyDeviceToHost, st));        // ... and the candidates its fast plan kernel left to the general one
+	word[LW_CHECKSUM] = word[LW_CHECKSUM + 1] = 0;
+	if (m.checksum) HIP_TRY(hipMemcpyAsync(&word[LW_CHECKSUM], l.d_sam_ctl + 2, 16, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(&word[LW_ALN_TRIVIAL], ws->d_aln_ctl + 36, 8, hipMemcpyDeviceToHost, st));        // ... and the pairs aln_trivial_kernel decided (in the place of the piece count, which nobody reads)
 	HIP_TRY(hipEventRecord(l.ev[6], st));
 	HIP_TRY(kgi_sync(ws));
-	if (tot[2] != 0) return fail(KG_ERR_NO_DEVICE, "kg_stream_map: %lld records were formatted to a size other than the one announced", (long long)tot[2]);
+	if (word[LW_FORMAT_ERRORS] != 0) return fail(KG_ERR_NO_DEVICE, "kg_stream_map: %lld records were formatted to a size other than the one announced", (long long)word[LW_FORMAT_ERRORS]);
 	std::sort(l.h_host_list, l.h_host_list + n_host);
-	out->n_reads = n; out->n_chunks = n_chunks;
-	out->sam = l.h_sam; out->sam_bytes = sam_bytes; out->sam_off = l.h_sam_off;
+	out->n_reads = n; out->n_chunks = m.n_chunks;
+	out->sam = l.h_sam; out->sam_bytes = m.sam_bytes; out->sam_off = l.h_sam_off;
 	out->records = l.h_records; out->n_records = n + extra;
 	out->chunk_stats = l.h_chunk_stats;
 	out->host_reads = l.h_host_list; out->n_host_reads = n_host;
 	out->cand_off = l.h_cand_off; out->cands = l.h_cands; out->cand_seeds = l.h_cand_seeds;
 	out->rec_start[0] = l.h_rec_hdr[0]; out->rec_start[1] = l.win.two_files ? l.h_rec_hdr[1] : nullptr;
 	l.have_batch = false;
-	{
-		// what the batch cost on the device, stage by stage, and what its search kernel fetched (kg_workspace_traffic's formula)
-		float sk = 0;
-		if (!grouped && ws->profiling && ws->ev[0]) sk = elapsed(ws->ev[0], ws->ev[1]);
-		const unsigned long long *c = l.h_ctl;
-		const double sa_bytes = ix->view.fsa32 ? 4.0 : 8.0;
-		double useful = grouped ? 0.0 : 8.0 * (double)c[17] + 32.0 * (double)c[18] + (double)c[25] + sa_bytes * (double)c[8] + 48.0 * (double)c[20] + 8.0 * (double)c[21] + 20.0 * (double)n + 32.0 * (double)c[1];
-		// (a group's launch counts once, with the lane that launched it)
-		if (grouped && group_leader) { sk = group_search_ms; useful = group_useful; }
-		std::lock_guard<std::mutex> lk(s->mu);
-		kg_stream_timing_t &t = s->total;
-		t.batches += 1; t.reads += n;
-		t.parse_ms += elapsed(l.ev[0], l.ev[1]); t.seed_ms += elapsed(l.ev[1], l.ev[2]); t.chain_ms += elapsed(l.ev[2], l.ev[3]);
-		t.align_ms += elapsed(l.ev[3], l.ev[4]); t.format_ms += elapsed(l.ev[4], l.ev[5]); t.copy_ms += elapsed(l.ev[5], l.ev[6]);
-		t.search_kernel_ms += sk; t.search_kernel_launches += (!grouped || group_leader) ? 1 : 0; t.search_useful_bytes += useful;
-		t.text_in_bytes += (double)((l.parsed.used[0] - l.win.begin[0]) + (l.win.two_files ? l.parsed.used[1] - l.win.begin[1] : 0));
-		t.text_out_bytes += (double)sam_bytes;
-		t.candidates += (double)totals[0]; t.candidate_seeds += (double)totals[1];
-		for (int i = 0; i < 8; ++i) t.aln_counts[i] += (double)tot[8 + i];
-		t.text_checksum[0] += (double)(uint64_t)tot[16]; t.text_checksum[1] += (double)(uint64_t)tot[17];
-		// the kernels' own launches of this batch (events around each, the lane's stream is synchronised)
-		for (int i = 0; i < KT_SLOTS; ++i) {
-			const int used = ws->kt.used[i];
-			if (!used) continue;
-			ws->kt.used[i] = 0;
-			for (int j = 0; j < used; ++j) t.kernel_ms[i] += elapsed(ws->kt.b[i][j], ws->kt.e[i][j]);
-			t.kernel_launches[i] += used;
-		}
+	return KG_OK;
+}
+
+// what the batch cost on the device, stage by stage, and what its search kernel fetched
+static void map_account(kg_stream *s, Lane &l, const MapCall &m)
+{
+	kg_workspace *ws = l.ws;
+	const int64_t *word = l.h_meta + FQM_WORDS;
+	float sk = 0;
+	if (!m.grouped && ws->profiling && ws->ev[0]) sk = elapsed(ws->ev[0], ws->ev[1]);
+	double useful = m.grouped ? 0.0 : search_useful_bytes(s->ix, l.h_ctl, m.n);
+	// (a group's launch counts once, with the lane that launched it)
+	if (m.grouped && m.group_leader) { sk = m.group_search_ms; useful = m.group_useful; }
+	std::lock_guard<std::mutex> lk(s->mu);
+	kg_stream_timing_t &t = s->total;
+	t.batches += 1; t.reads += m.n;
+	t.parse_ms += elapsed(l.ev[0], l.ev[1]); t.seed_ms += elapsed(l.ev[1], l.ev[2]); t.chain_ms += elapsed(l.ev[2], l.ev[3]);
+	t.align_ms += elapsed(l.ev[3], l.ev[4]); t.format_ms += elapsed(l.ev[4], l.ev[5]); t.copy_ms += elapsed(l.ev[5], l.ev[6]);
+	t.search_kernel_ms += sk; t.search_kernel_launches += (!m.grouped || m.group_leader) ? 1 : 0; t.search_useful_bytes += useful;
+	t.text_in_bytes += (double)((l.parsed.used[0] - l.win.begin[0]) + (l.win.two_files ? l.parsed.used[1] - l.win.begin[1] : 0));
+	t.text_out_bytes += (double)m.sam_bytes;
+	t.candidates += (double)m.totals[0]; t.candidate_seeds += (double)m.totals[1];
+	for (int i = 0; i < 8; ++i) t.aln_counts[i] += (double)word[LW_ALN_COUNTS + i];
+	t.text_checksum[0] += (double)(uint64_t)word[LW_CHECKSUM]; t.text_checksum[1] += (double)(uint64_t)word[LW_CHECKSUM + 1];
+	// the kernels' own launches of this batch (events around each, the lane's stream is synchronised)
+	for (int i = 0; i < KT_SLOTS; ++i) {
+		const int used = ws->kt.used[i];
+		if (!used) continue;
+		ws->kt.used[i] = 0;
+		for (int j = 0; j < used; ++j) t.kernel_ms[i] += elapsed(ws->kt.b[i][j], ws->kt.e[i][j]);
+		t.kernel_launches[i] += used;
 	}
+}
+
+int kg_stream_map(kg_stream *s, int lane, const kg_stream_params *prm, kg_stream_result *out)
+{
+	if (!s || !prm || !out || lane < 0 || lane >= (int)s->lanes.size()) return fail(KG_ERR_ARG, "kg_stream_map: bad argument");
+	Lane &l = s->lanes[(size_t)lane];
+	if (!l.have_batch) return fail(KG_ERR_ARG, "kg_stream_map: no parsed batch in lane %d (kg_stream_parse first)", lane);
+	memset(out, 0, sizeof(*out));
+	HIP_TRY(hipSetDevice(s->ix->device));
+	KtUse kt_use(l.ws->profiling ? &l.ws->kt : nullptr);
+	MapCall m;
+	m.prm = prm;
+	m.n = l.parsed.n_reads;
+	m.n_chunks = (int)l.parsed.n_chunks;
+	m.grouped = !s->groups.empty();
+	GroupTurn turn;                                    // (released on every way out of this function)
+	int rc;
+	if ((rc = map_seed(s, lane, m, turn)) != KG_OK) return rc;
+	if ((rc = map_chain(l, m)) != KG_OK) return rc;
+	if ((rc = map_report(l, m)) != KG_OK) return rc;
+	if ((rc = map_size_text(s, l, m)) != KG_OK) return rc;
+	if ((rc = map_format(s, l, m)) != KG_OK) return rc;
+	// (grouped seeding) the turn is kept until the batch is back on the host.  Passing it on here -- so that this lane's copies overlap the
+	// next lane's kernels, KG_GROUP_TURN_EARLY=1 -- gives the same FASTQ -> SAM rate at 100 M reads (29.4-29.9 M against 29.8-30.4 M
+	// mapped reads/s) while the next lane's first kernel then waits behind this one's copies: chain_kernel 5.0 ms per launch instead of 0.35,
+	// the stage sums twice as long (profiles/r04u_trace_chain.log, r04v_ab_turn_late.log); the other group's lanes overlap either way.
+	static const bool turn_early = getenv("KG_GROUP_TURN_EARLY") != nullptr;
+	if (turn_early) turn.release();
+	if ((rc = map_copy_out(l, m, out)) != KG_OK) return rc;
+	map_account(s, l, m);
 	return KG_OK;
 }
 
@@ -758,10 +870,9 @@ int kg_stream_group_absent(kg_stream *s, int lane, int rounds)
 	sg.absent_rounds[j] = rounds;
 	if (rounds == 0) sg.aborted = false;               // (a new run: the lanes take part again; an aborted run's half-finished round is forgotten)
 	// the round may be complete now: everybody else has arrived and waits
-	int accounted = sg.arrived;
-	for (int i = 0; i < sg.size; ++i) accounted += (!sg.present[i] && sg.absent_rounds[i] != 0) ? 1 : 0;
-	if (rounds != 0 && sg.arrived > 0 && accounted >= sg.size) sg.cv.notify_all();     // a waiting lane runs the round (group_seed's loop)
-	if (rounds > 0 && sg.arrived == 0 && accounted >= sg.size) {
+	const bool complete = round_complete(sg);
+	if (rounds != 0 && sg.arrived > 0 && complete) sg.cv.notify_all();     // a waiting lane runs the round (group_seed's loop)
+	if (rounds > 0 && sg.arrived == 0 && complete) {
 		// every lane of the group sits this round out: nobody will run it, so it is over here (the lanes would wait for it for ever)
 		for (int i = 0; i < sg.size; ++i)
 			if (sg.absent_rounds[i] > 0) sg.absent_rounds[i]--;
@@ -803,13 +914,13 @@ int kg_stream_fetch(kg_stream *s, int lane, int64_t first, int64_t count)
 	kg_workspace *ws = l.ws;
 	HIP_TRY(hipSetDevice(ws->ix->device));
 	hipStream_t st = ws->stream;
-	int64_t *tot = l.h_meta + FQM_WORDS;              // (words 18 .. 19 of the lane's page-locked scratch: the seed offsets at either end)
+	int64_t *seeds_at = l.h_meta + FQM_WORDS + LW_FETCH_SEEDS;
 	HIP_TRY(hipMemcpyAsync(l.h_records + first, l.d_records + first, sizeof(kg_aln_record) * (size_t)count, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(l.h_cand_off + first, ws->d_cand_off + first, 8 * (size_t)(count + 1), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(&tot[18], ws->d_cseed_off + first, 8, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(&tot[19], ws->d_cseed_off + first + count, 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(&seeds_at[0], ws->d_cseed_off + first, 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(&seeds_at[1], ws->d_cseed_off + first + count, 8, hipMemcpyDeviceToHost, st));
 	HIP_TRY(kgi_sync(ws));
-	const int64_t c0 = l.h_cand_off[first], c1 = l.h_cand_off[first + count], s0 = tot[18], s1 = tot[19];
+	const int64_t c0 = l.h_cand_off[first], c1 = l.h_cand_off[first + count], s0 = seeds_at[0], s1 = seeds_at[1];
 	if (c0 < 0 || c1 < c0 || c1 > l.h_cand_capacity || s0 < 0 || s1 < s0 || s1 > l.h_cand_capacity) return fail(KG_ERR_NO_DEVICE, "kg_stream_fetch: the batch's candidate offsets are not what kg_stream_map left");
 	if (c1 > c0) HIP_TRY(hipMemcpyAsync(l.h_cands + c0, ws->d_dense_cands + c0, sizeof(kg_candidate) * (size_t)(c1 - c0), hipMemcpyDeviceToHost, st));
 	if (s1 > s0) HIP_TRY(hipMemcpyAsync(l.h_cand_seeds + s0, ws->d_dense_seeds + s0, sizeof(kg_seed) * (size_t)(s1 - s0), hipMemcpyDeviceToHost, st));

@@ -1304,11 +1304,13 @@ hipError_t launch_group_rebase(const int64_t *g_seed_off, int64_t n, int64_t fir
 	return hipGetLastError();
 }
 
-hipError_t launch_sam_size(const SamArgs &a, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream)
+// the size of every read's text and their scan, then the text itself; bam: BAM records in the place of the SAM lines (they count into the same slots)
+hipError_t launch_text_size(const SamArgs &a, bool bam, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream)
 {
 	kt_begin(KT_SAM_SIZE, stream);
 	hipLaunchKernelGGL(sam_reset_kernel, dim3(1), dim3(64), 0, stream, a);
-	hipLaunchKernelGGL(sam_size_kernel, dim3(grid_of(a.n_reads, 256, n_cu * 16)), dim3(256), 0, stream, a);
+	if (bam) hipLaunchKernelGGL(bam_size_kernel, dim3(grid_of(a.n_reads, 256, n_cu * 16)), dim3(256), 0, stream, a);
+	else hipLaunchKernelGGL(sam_size_kernel, dim3(grid_of(a.n_reads, 256, n_cu * 16)), dim3(256), 0, stream, a);
 	size_t tb = scan_temp_bytes;
 	Wide32Iter it(a.sam_len, Widen32());
 	hipError_t e = hipcub::DeviceScan::ExclusiveSum(scan_temp, tb, it, a.sam_off, (int)(a.n_reads + 1), stream);
@@ -1317,34 +1319,12 @@ hipError_t launch_sam_size(const SamArgs &a, void *scan_temp, size_t scan_temp_b
 	return hipGetLastError();
 }
 
-hipError_t launch_sam_format(const SamArgs &a, int n_cu, hipStream_t stream)
+hipError_t launch_text_format(const SamArgs &a, bool bam, int n_cu, hipStream_t stream)
 {
 	if (a.n_reads <= 0) return hipSuccess;
 	kt_begin(KT_SAM_FORMAT, stream);
-	hipLaunchKernelGGL(sam_format_kernel, dim3(grid_of((a.n_reads + 63) / 64, 1, n_cu * 64)), dim3(64), 0, stream, a);
-	kt_end(KT_SAM_FORMAT, stream);
-	return hipGetLastError();
-}
-
-// the same two steps for BAM records: they count into the slots of the SAM kernels they stand in for
-hipError_t launch_bam_size(const SamArgs &a, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream)
-{
-	kt_begin(KT_SAM_SIZE, stream);
-	hipLaunchKernelGGL(sam_reset_kernel, dim3(1), dim3(64), 0, stream, a);
-	hipLaunchKernelGGL(bam_size_kernel, dim3(grid_of(a.n_reads, 256, n_cu * 16)), dim3(256), 0, stream, a);
-	size_t tb = scan_temp_bytes;
-	Wide32Iter it(a.sam_len, Widen32());
-	hipError_t e = hipcub::DeviceScan::ExclusiveSum(scan_temp, tb, it, a.sam_off, (int)(a.n_reads + 1), stream);
-	if (e != hipSuccess) return e;
-	kt_end(KT_SAM_SIZE, stream);
-	return hipGetLastError();
-}
-
-hipError_t launch_bam_format(const SamArgs &a, int n_cu, hipStream_t stream)
-{
-	if (a.n_reads <= 0) return hipSuccess;
-	kt_begin(KT_SAM_FORMAT, stream);
-	hipLaunchKernelGGL(bam_format_kernel, dim3(grid_of((a.n_reads + 63) / 64, 1, n_cu * 64)), dim3(64), 0, stream, a);
+	if (bam) hipLaunchKernelGGL(bam_format_kernel, dim3(grid_of((a.n_reads + 63) / 64, 1, n_cu * 64)), dim3(64), 0, stream, a);
+	else hipLaunchKernelGGL(sam_format_kernel, dim3(grid_of((a.n_reads + 63) / 64, 1, n_cu * 64)), dim3(64), 0, stream, a);
 	kt_end(KT_SAM_FORMAT, stream);
 	return hipGetLastError();
 }

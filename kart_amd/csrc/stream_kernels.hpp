@@ -88,11 +88,10 @@ size_t fa_scan_temp_bytes(int64_t max_lines);      // the scan over FqWindow::li
 // line index + record table of both windows, read lengths and their scan, the plan (meta)
 hipError_t launch_fq_parse(const FqArgs &a, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream);
 hipError_t launch_fq_materialise(const FqArgs &a, int n_cu, hipStream_t stream);
-hipError_t launch_sam_size(const SamArgs &a, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream);
-hipError_t launch_sam_format(const SamArgs &a, int n_cu, hipStream_t stream);
-// BAM records in the place of the text (same arguments, same outputs: sam_len / sam_off / sam hold the records' bytes)
-hipError_t launch_bam_size(const SamArgs &a, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream);
-hipError_t launch_bam_format(const SamArgs &a, int n_cu, hipStream_t stream);
+// the text of the batch: sizes and their scan, then the bytes; bam: BAM records in the place of the SAM lines (same arguments, same outputs:
+// sam_len / sam_off / sam hold the records' bytes)
+hipError_t launch_text_size(const SamArgs &a, bool bam, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream);
+hipError_t launch_text_format(const SamArgs &a, bool bam, int n_cu, hipStream_t stream);
 hipError_t launch_sam_checksum(const SamArgs &a, int n_cu, hipStream_t stream);      // measurement aid: ctl[2] += byte sum, ctl[3] += line feeds of the text
 // grouped seeding: a lane's parsed batch published as a segment of its group's batch; the lane's seed offsets cut out of the group's
 hipError_t launch_group_publish(const int64_t *local_off, int64_t n, int64_t slots, int64_t enc_base, int64_t *g_off, int32_t *g_len, int n_cu, hipStream_t stream);
