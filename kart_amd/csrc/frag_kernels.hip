@@ -5,7 +5,7 @@
 // (GenerateSimplePairsFromFragmentPair, src/KmerAnalysis.cpp:104-179), runs IdentifyNormalPairs(rLen, gLen, ...) on those
 // (src/AlignmentCandidates.cpp:420-490 with its three seed filters, :235-418), and aligns what lies between them: literal
 // stretches, nw_alignment for the sub-fragments, and -- -pacbio only -- the same procedure again for a sub-fragment with a side
-// above 300 (the recursion at :197).  aln_partition_kernel (align_kernels.hip) does this for short-read fragments (<= 255
+// above 300 (the recursion at :197).  aln_partition_kernel (align_plan.hip) does this for short-read fragments (<= 255
 // bases, <= 12 matches, no recursion); this file is the general form:
 //   frag_partition_kernel  one wave per task (a fragment pair).  The read fragment and the text window go into the LDS as 2-bit
 //                          codes; every lane scans diagonals for runs of >= 8 equal bases (32 bases per step); the runs are

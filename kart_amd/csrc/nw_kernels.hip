@@ -34,7 +34,7 @@ __device__ __forceinline__ int nt4_code(unsigned char ch)  // nst_nt4_table, src
 }
 
 // A pair of the batch: offsets/lengths either from the two prefix-sum arrays of the C ABI (kg_nw_batch*) or from a job
-// descriptor the alignment stage wrote on the device (align_kernels.hip).  In descriptor mode sequence 2 is read straight
+// descriptor the alignment stage wrote on the device (align_plan.hip).  In descriptor mode sequence 2 is read straight
 // from the 2-bit text of the index (its codes ARE nst_nt4_table's), sequence 1 from the read characters.
 struct NwPair {
 	int64_t o1, o2, oo;

@@ -148,7 +148,7 @@ struct ChainArgs {
 };
 hipError_t launch_chain_batch(const ChainArgs &a, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream);
 
-// a gap-closing job written on the device by the alignment stage (align_kernels.hip)
+// a gap-closing job written on the device by the alignment stage (align_plan.hip)
 struct NwJobDesc {
 	int64_t o1;           // offset of the read-side fragment in the read characters
 	int64_t o2;           // text coordinate of the genome-side fragment

@@ -292,8 +292,7 @@ def test_records_do_not_depend_on_the_arrangement(rep, whole):
 
 # ---- every alternative form of the stage, through the product binary -----------------------------------------------------------------------------
 FORMS = [{"KG_ALN_NO_HEAVY": "1"}, {"KG_ALN_PAIR_HEAVY": "1"}, {"KG_ALN_PAIR_HEAVY": "1000000"}, {"KG_ALN_NO_TRIVIAL": "1"}, {"KG_ALN_NO_FAST": "1"},
-         {"KG_ALN_NO_BINS": "1"}, {"KG_ALN_FINISH_LANES": "1"}, {"KG_ALN_FINISH_WAVE": "1"}, {"KG_ALN_FINISH_G16": "1"}, {"KG_ALN_PLAN_GROUP": "1"},
-         {"KG_ALN_INLINE": "1"}, {"KG_RESCUE_SCAN": "1"}, {}, {"KART_AMD_NO_STREAM": "1"}]
+         {"KG_ALN_NO_BINS": "1"}, {"KG_RESCUE_SCAN": "1"}, {}, {"KART_AMD_NO_STREAM": "1"}]
 
 
 @pytest.fixture(scope="module")

@@ -36,7 +36,7 @@ def test_golden_sam(case, product_binary, tmp_path):
 def test_full_lists_hand_their_reads_to_the_host(env, product_binary, tmp_path):
     """aln_plan_kernel / aln_partition_kernel with the spill, job or op-byte list full (lists as short as a few entries, abi.hip
     KG_DBG_*_CAPACITY): the candidates beyond go back to the host, and what they had already taken INSIDE the lists is left as an
-    empty entry -- aln_finish_kernel and the NW kernels walk every entry below the counters.  Several batches on one workspace, so
+    empty entry -- aln_finish_group_kernel and the NW kernels walk every entry below the counters.  Several batches on one workspace, so
     that a stale entry of the batch before would be found.  Same SAM as the reference's."""
     for case in ("pe", "pe_m"):
         if case not in CASES:
