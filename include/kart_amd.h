@@ -321,6 +321,18 @@ int  kg_nw_batch_device(kg_index *ix, const char *d_frag1, const int64_t *d_off1
 int  kg_fragments_batch(kg_index *ix, const char *frag1, const int64_t *off1, const int64_t *gpos, const int32_t *glen, int64_t n,
                         int pacbio, int max_gaps, uint8_t *ops, const int64_t *ops_off, int32_t *aln_len, uint8_t *status);
 
+/* ---- bytes in, BGZF blocks out -------------------------------------------------------------------------------------------- */
+/* src[0, src_bytes) as BGZF blocks (SAM/BAM specification v1, 4.1: every block an independent gzip member with the "BC" field, at most 0xff00 bytes
+ * of payload and 64 KiB in all), compressed on the device: LZ77 (distance <= 32768, length 3 .. 258) and one dynamic-Huffman block per member, or a
+ * stored block where that would not be smaller.  Host pointers; the call copies in and out.  `cuts` are n_cuts ascending byte offsets, cuts[0] == 0
+ * and cuts[n_cuts - 1] == src_bytes (else KG_ERR_ARG): no block straddles a cut, every non-empty range between two neighbouring cuts is split into
+ * payloads of at most 0xff00 bytes, an empty range makes no block.  Out: the members back to back in dst, *n_blocks, and block_src / block_off
+ * [*n_blocks + 1]: block i holds src[block_src[i], block_src[i+1]) and is dst[block_off[i], block_off[i+1]).  Tables of fewer than the blocks the
+ * cuts make (max_blocks) or a dst smaller than the members is KG_ERR_CAPACITY, the message names the need; nothing is written past either.
+ * The bytes are not zlib's -- no reader needs them to be, only the inflated stream -- but they depend on the input alone: a second call gives the same. */
+int  kg_bgzf_deflate(int device, const uint8_t *src, int64_t src_bytes, const int64_t *cuts, int64_t n_cuts,
+                     uint8_t *dst, int64_t dst_capacity, int64_t *block_src, int64_t *block_off, int64_t max_blocks, int64_t *n_blocks);
+
 /* ---- FASTQ text in, SAM text (or BAM records) out ------------------------------------------------------------------- */
 /* The reference's worker takes a chunk of reads from GetNextChunk (src/GetData.cpp:109-143: four getline() calls per record,
  * the name cut out of the header by IdentifyHeaderBegPos / EndPos, mate 2 reverse-complemented), maps it, and prints every
@@ -335,7 +347,8 @@ int  kg_fragments_batch(kg_index *ix, const char *frag1, const int64_t *off1, co
  * newline) to the sequence; the quality column of every record is then "*".  The inflated text of a gz file of either format: kg_stream_window::gz_lines.
  * The records come back as SAM lines or, after kg_stream_set_format(KG_STREAM_FORMAT_BAM), as uncompressed BAM records (SAM/BAM
  * specification v1, 4.2: block_size first) -- what the reference's -bo makes of the same lines with sam_parse1 / sam_write1
- * (src/Mapping.cpp:610-620) before BGZF compresses them; compression stays with the caller.
+ * (src/Mapping.cpp:610-620) before BGZF compresses them.  Compression stays with the caller in that format; KG_STREAM_FORMAT_BAM_BGZF
+ * compresses the records on the device as well and hands the BGZF blocks over beside them (kg_bgzf_deflate: the same kernels on any bytes).
  *
  *   per batch:  fill kg_stream_staging(lane, f) -> kg_stream_upload (any number of pieces) -> kg_stream_parse -> kg_stream_map
  */
@@ -352,10 +365,13 @@ typedef struct {
 } kg_stream_config;
 int   kg_stream_open(kg_index *ix, const kg_stream_config *cfg, kg_stream **out);
 void  kg_stream_close(kg_stream *s);
-/* What kg_stream_map makes of the records: SAM text (the default) or BAM records.  Holds for every later kg_stream_map on all lanes; call it while no
- * lane is inside a call (the lanes' output buffers grow to what the larger format needs).  An unknown value is KG_ERR_ARG. */
+/* What kg_stream_map makes of the records: SAM text (the default), BAM records, or BAM records and the BGZF blocks that hold them.  Holds for
+ * every later kg_stream_map on all lanes; call it while no lane is inside a call (the lanes' output buffers grow to what the larger format needs;
+ * the first KG_STREAM_FORMAT_BAM_BGZF run allocates, per lane, a slot of 64 KiB for every block a batch can make and a buffer for the gathered
+ * blocks: about twice the output buffer again).  An unknown value is KG_ERR_ARG. */
 #define KG_STREAM_FORMAT_SAM 0
 #define KG_STREAM_FORMAT_BAM 1
+#define KG_STREAM_FORMAT_BAM_BGZF 2   /* the records exactly as KG_STREAM_FORMAT_BAM, and kg_stream_result::bgzf .. block_off */
 int   kg_stream_set_format(kg_stream *s, int format);
 /* What kg_stream_parse takes the text for: FASTQ (the default) or FASTA.  Holds for every later kg_stream_parse on all lanes; call it while no lane is
  * inside a call (the first FASTA run allocates the per-line arrays of its record kernels).  An unknown value is KG_ERR_ARG. */
@@ -416,6 +432,14 @@ typedef struct {
 	const kg_candidate *cands;
 	const kg_seed *cand_seeds;
 	const uint32_t *rec_start[2];    /* staging offset of the header line of record j of file f (read r = record r/2 of file r%2 with two files) */
+	/* KG_STREAM_FORMAT_BAM_BGZF (else NULL / 0): the records as BGZF blocks (SAMv1 4.1) deflated on the device.  No block straddles the first byte of a
+	 * chunk (chunk_reads reads) or the place of a read handed back, so a caller that maps some chunks again or fills the handed-back reads in can
+	 * take the blocks of every untouched piece as they are.  The bytes depend on the records alone: the same batch gives the same blocks */
+	const uint8_t *bgzf;             /* the members back to back (page-locked, the lane's) */
+	int64_t bgzf_bytes;
+	int64_t n_blocks;
+	const int64_t *block_src;        /* [n_blocks + 1] block i holds sam[block_src[i], block_src[i+1]) (at most 0xff00 bytes) */
+	const int64_t *block_off;        /* [n_blocks + 1] ... and is bgzf[block_off[i], block_off[i+1]) */
 } kg_stream_result;
 /* seeding (FastMode), chaining, the per-read report (kg_align_batch) and the SAM text for the batch kg_stream_parse left in the
  * lane.  The result's arrays belong to the lane: valid until its next kg_stream_parse. */
@@ -448,7 +472,7 @@ typedef struct {
 	/* the batches' kernels one by one (HIP events around each launch on the lane's stream; other lanes' kernels share the device):
 	 * [0] chain, [1] aln_pair, [2] aln_rescue + post_rescue, [3] aln_plan_fast, [4] aln_plan, [5] aln_partition, [6] the NW kernels,
 	 * [7] aln_finish, [8] aln_final, [9] sam_size + scan, [10] sam_format, [11] fq_count / index / record / plan, [12] fq_materialise,
-	 * [13] locate + sort, [14] aln_trivial */
+	 * [13] locate + sort, [14] aln_trivial, [15] the BGZF blocks' plan + deflate + pack (KG_STREAM_FORMAT_BAM_BGZF) */
 	double kernel_ms[16];
 	int64_t kernel_launches[16];
 	/* what the alignment stage's lists held, summed over the batches: [0] candidates parked for NW, [1] NW jobs, [2] bytes of their op strings,

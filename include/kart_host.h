@@ -57,6 +57,9 @@ typedef struct {
 	int32_t lanes;
 	int32_t pad2;
 	double  text_checksum[2];        /* kg_stream_timing_t::text_checksum (KG_STREAM_CHECKSUM) */
+	/* -bo through the device stream: bytes of the BGZF blocks of its chunks in the file that the device compressed (-bz device) and that the host's zlib
+	 * did (the header, the end-of-file block and what the general reader maps are the host's always and are not counted) */
+	int64_t bgzf_device_bytes, bgzf_host_bytes;
 } kh_stats_t;
 
 const char *kh_last_error(void);

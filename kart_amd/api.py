@@ -27,7 +27,7 @@ KG_OK = 0
 KG_MODE_FAST, KG_MODE_SENSITIVE = 0, 1
 KG_INPUT_ASCII = 0x100   # OR into mode: reads are given as characters, encoded on the device
 KG_SA_SAMPLED, KG_SA_FULL = 0, 1
-KG_STREAM_FORMAT_SAM, KG_STREAM_FORMAT_BAM = 0, 1   # kg_stream_set_format
+KG_STREAM_FORMAT_SAM, KG_STREAM_FORMAT_BAM, KG_STREAM_FORMAT_BAM_BGZF = 0, 1, 2   # kg_stream_set_format
 KG_STREAM_INPUT_FASTQ, KG_STREAM_INPUT_FASTA = 0, 1   # kg_stream_set_input
 KG_SA_AUTO = -1                        # full below 2^32 text symbols; above: wide where the device has room, else compact (the host pipeline's default)
 KG_SA_FULL40 = 5                       # the compact index: 5-byte suffix-array entries, a quarter of the q-mer table, no triple planes
@@ -56,6 +56,7 @@ ABI_SYMBOLS = (
     "kg_fragments_batch", "kg_longread_batch", "kg_longread_reasons",
     "kg_stream_open", "kg_stream_close", "kg_stream_staging", "kg_stream_upload", "kg_stream_parse", "kg_stream_map", "kg_stream_fetch", "kg_stream_fetch_reads", "kg_stream_timing",
     "kg_stream_group_absent", "kg_stream_group_abort", "kg_stream_set_format", "kg_stream_set_input",
+    "kg_bgzf_deflate",
 )
 
 
@@ -130,7 +131,8 @@ class StreamParams(C.Structure):
 class StreamResult(C.Structure):
     _fields_ = [("n_reads", C.c_int64), ("n_chunks", C.c_int64), ("sam", C.c_void_p), ("sam_bytes", C.c_int64), ("sam_off", C.POINTER(C.c_int64)),
                 ("records", C.c_void_p), ("n_records", C.c_int64), ("chunk_stats", C.c_void_p), ("host_reads", C.POINTER(C.c_int32)), ("n_host_reads", C.c_int64),
-                ("cand_off", C.POINTER(C.c_int64)), ("cands", C.c_void_p), ("cand_seeds", C.c_void_p), ("rec_start", C.POINTER(C.c_uint32) * 2)]
+                ("cand_off", C.POINTER(C.c_int64)), ("cands", C.c_void_p), ("cand_seeds", C.c_void_p), ("rec_start", C.POINTER(C.c_uint32) * 2),
+                ("bgzf", C.c_void_p), ("bgzf_bytes", C.c_int64), ("n_blocks", C.c_int64), ("block_src", C.POINTER(C.c_int64)), ("block_off", C.POINTER(C.c_int64))]
 
 
 class StreamTiming(C.Structure):
@@ -225,6 +227,7 @@ def load_library() -> C.CDLL:
     L.kg_stream_set_format.argtypes = [C.c_void_p, C.c_int]
     L.kg_stream_set_input.argtypes = [C.c_void_p, C.c_int]
     L.kg_stream_timing.argtypes = [C.c_void_p, C.POINTER(StreamTiming), C.c_int]
+    L.kg_bgzf_deflate.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     _lib = L
     return L
 
@@ -240,6 +243,28 @@ def device_count() -> int:
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+BGZF_PAYLOAD = 0xff00                  # bytes of payload per BGZF block at most (htslib's size)
+
+
+def bgzf_deflate(data: bytes, cuts=None, device: int = 0, dst_capacity: int | None = None, max_blocks: int | None = None):
+    """kg_bgzf_deflate: `data` as BGZF blocks compressed on the device -> (the members back to back, block_src, block_off).  `cuts`: ascending byte
+    offsets from 0 to len(data) that no block straddles (default: none but the two ends); block i holds data[block_src[i]:block_src[i+1]] and is
+    bgzf[block_off[i]:block_off[i+1]].  dst_capacity / max_blocks default to what the cuts can need at most; smaller ones make the call fail."""
+    cuts = np.ascontiguousarray([0, len(data)] if cuts is None else cuts, dtype=np.int64)
+    spans = np.maximum(np.diff(cuts), 0)
+    need = int(((spans + BGZF_PAYLOAD - 1) // BGZF_PAYLOAD).sum())
+    max_blocks = need if max_blocks is None else int(max_blocks)
+    dst_capacity = len(data) + 31 * need if dst_capacity is None else int(dst_capacity)
+    src = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)
+    dst = np.zeros(max(1, dst_capacity), dtype=np.uint8)
+    block_src = np.zeros(max_blocks + 1, dtype=np.int64)
+    block_off = np.zeros(max_blocks + 1, dtype=np.int64)
+    n = C.c_int64()
+    _check(load_library().kg_bgzf_deflate(device, _ptr(src), len(data), _ptr(cuts), len(cuts), _ptr(dst), dst_capacity, _ptr(block_src), _ptr(block_off),
+                                          max_blocks, C.byref(n)), "kg_bgzf_deflate")
+    return dst[:int(block_off[n.value])].tobytes(), block_src[:n.value + 1].copy(), block_off[:n.value + 1].copy()
 
 
 def concat_reads(reads):
@@ -506,7 +531,7 @@ class Index:
 class Stream:
     """kg_stream_*: FASTQ or FASTA text in, SAM text or BAM records out (GetNextChunk ... Output*Alignments of the reference on the device)."""
 
-    FORMATS = {"sam": KG_STREAM_FORMAT_SAM, "bam": KG_STREAM_FORMAT_BAM}
+    FORMATS = {"sam": KG_STREAM_FORMAT_SAM, "bam": KG_STREAM_FORMAT_BAM, "bgzf": KG_STREAM_FORMAT_BAM_BGZF}
     INPUTS = {"fastq": KG_STREAM_INPUT_FASTQ, "fasta": KG_STREAM_INPUT_FASTA}
 
     def __init__(self, index: "Index", max_reads: int = 16000, max_window: int = 8 << 20, lanes: int = 1, seed_group: int = 0):
@@ -517,6 +542,7 @@ class Stream:
         _check(self.lib.kg_stream_open(index.h, C.byref(cfg), C.byref(h)), "kg_stream_open")
         self.h = h
         self.max_window = max_window
+        self.last_blocks = None                        # format "bgzf": (bgzf bytes, block_src, block_off) of the last map(); else None
 
     def close(self):
         if self.h:
@@ -524,7 +550,8 @@ class Stream:
             self.h = None
 
     def set_format(self, fmt):
-        """what map() returns per read from here on: "sam" (the default) lines, "bam" uncompressed BAM records (block_size first)"""
+        """what map() returns per read from here on: "sam" (the default) lines, "bam" uncompressed BAM records (block_size first), "bgzf" the same
+        records, with the BGZF blocks the device compressed them into in `last_blocks`"""
         _check(self.lib.kg_stream_set_format(self.h, self.FORMATS.get(fmt, fmt) if isinstance(fmt, str) else int(fmt)), "kg_stream_set_format")
 
     def set_input(self, kind):
@@ -579,6 +606,11 @@ class Stream:
         off = np.ctypeslib.as_array(res.sam_off, shape=(n + 1,)).copy()
         sam = C.string_at(res.sam, res.sam_bytes)
         host = [int(res.host_reads[i]) for i in range(res.n_host_reads)]
+        self.last_blocks = None
+        if res.block_src:
+            nb = res.n_blocks
+            self.last_blocks = (C.string_at(res.bgzf, res.bgzf_bytes), np.ctypeslib.as_array(res.block_src, shape=(nb + 1,)).copy(),
+                                np.ctypeslib.as_array(res.block_off, shape=(nb + 1,)).copy())
         return [sam[off[i]:off[i + 1]] for i in range(n)], host
 
     def timing(self, reset: bool = False) -> dict:
@@ -609,7 +641,8 @@ class HostStats(C.Structure):
                 ("stream_reads", C.c_int64), ("stream_batches", C.c_int64), ("stage_ms", C.c_double * 6), ("search_kernel_ms", C.c_double),
                 ("search_kernel_launches", C.c_int64), ("search_useful_bytes", C.c_double), ("text_in_bytes", C.c_double), ("text_out_bytes", C.c_double),
                 ("candidates", C.c_double), ("candidate_seeds", C.c_double), ("kernel_ms", C.c_double * 16), ("kernel_launches", C.c_int64 * 16), ("aln_counts", C.c_double * 8),
-                ("lane_seconds", C.c_double * 6), ("lanes", C.c_int32), ("pad2", C.c_int32), ("text_checksum", C.c_double * 2)]
+                ("lane_seconds", C.c_double * 6), ("lanes", C.c_int32), ("pad2", C.c_int32), ("text_checksum", C.c_double * 2),
+                ("bgzf_device_bytes", C.c_int64), ("bgzf_host_bytes", C.c_int64)]
 
     def as_dict(self):
         return {n: (list(getattr(self, n)) if n.startswith(("kernel_", "stage_", "aln_counts")) else getattr(self, n)) for n, _ in self._fields_}

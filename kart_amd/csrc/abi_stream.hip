@@ -7,6 +7,7 @@
 // the reference's N workers each on their own chunk, src/Mapping.cpp:716-717).
 #include "abi_internal.hpp"
 #include "stream_kernels.hpp"
+#include "bgzf_kernels.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -30,6 +31,7 @@ enum LaneWord {
 	LW_ALN_GENERAL = 15,                               // and the candidates its fast plan kernel left to the general one
 	LW_CHECKSUM = 16,                                  // [16, 18) sam_checksum_kernel's sums (KG_STREAM_CHECKSUM)
 	LW_FETCH_SEEDS = 18,                               // [18, 20) kg_stream_fetch: the candidate seeds' offsets at either end of the reads asked for
+	LW_BGZF = 20,                                      // [20, 24) KG_STREAM_FORMAT_BAM_BGZF: the BGZF launch's control words (BgzfArgs::ctl)
 	LW_WORDS = 24
 };
 
@@ -51,6 +53,18 @@ struct Lane {
 	unsigned long long *d_sam_ctl = nullptr;
 	uint8_t *d_sam = nullptr;
 	int64_t d_sam_capacity = 0;
+	// KG_STREAM_FORMAT_BAM_BGZF (bgzf_room: allocated by the first kg_stream_set_format that asks for it, grown by a batch that needs more)
+	int64_t *d_cuts = nullptr, *d_range_first = nullptr;       // [max_reads + 8]
+	int64_t *d_block_src = nullptr, *d_block_off = nullptr;    // [bgzf_blocks + 1]
+	int32_t *d_block_bytes = nullptr;
+	uint8_t *d_slots = nullptr, *d_bgzf = nullptr;             // bgzf_blocks slots of 64 KiB; the members gathered
+	int64_t bgzf_blocks = 0, d_bgzf_capacity = 0;
+	unsigned long long *d_bgzf_ctl = nullptr;
+	void *d_bgzf_scan = nullptr;
+	size_t bgzf_scan_bytes = 0;
+	uint8_t *h_bgzf = nullptr;                                 // page-locked, as are the tables
+	int64_t h_bgzf_capacity = 0;
+	int64_t *h_block_src = nullptr, *h_block_off = nullptr;
 	// page-locked
 	char *h_text[2] = {nullptr, nullptr};
 	int64_t *h_meta = nullptr;                         // [FQM_WORDS] the parser's plan + [LW_WORDS] what the batch's small copies land in (LaneWord)
@@ -170,10 +184,12 @@ void free_lane(Lane &l)
 		if (l.h_text[f]) (void)hipHostFree(l.h_text[f]);
 		if (l.h_rec_hdr[f]) (void)hipHostFree(l.h_rec_hdr[f]);
 	}
-	for (void *p : {(void *)l.d_meta, (void *)l.d_read_len, l.d_scan, (void *)l.d_sam_len, (void *)l.d_host_list, (void *)l.d_sam_off, (void *)l.d_sam_ctl, (void *)l.d_sam})
+	for (void *p : {(void *)l.d_meta, (void *)l.d_read_len, l.d_scan, (void *)l.d_sam_len, (void *)l.d_host_list, (void *)l.d_sam_off, (void *)l.d_sam_ctl, (void *)l.d_sam,
+	                (void *)l.d_cuts, (void *)l.d_range_first, (void *)l.d_block_src, (void *)l.d_block_off, (void *)l.d_block_bytes, (void *)l.d_slots, (void *)l.d_bgzf,
+	                (void *)l.d_bgzf_ctl, l.d_bgzf_scan})
 		if (p) (void)hipFree(p);
 	for (void *p : {(void *)l.h_meta, (void *)l.h_sam, (void *)l.h_sam_off, (void *)l.h_cand_off, (void *)l.h_host_list, (void *)l.h_records, (void *)l.h_chunk_stats,
-	                (void *)l.h_cands, (void *)l.h_cand_seeds, (void *)l.h_ctl})
+	                (void *)l.h_cands, (void *)l.h_cand_seeds, (void *)l.h_ctl, (void *)l.h_bgzf, (void *)l.h_block_src, (void *)l.h_block_off})
 		if (p) (void)hipHostFree(p);
 	for (hipEvent_t e : l.ev)
 		if (e) (void)hipEventDestroy(e);
@@ -202,7 +218,7 @@ FqWindow window_of(const kg_stream *s, const Lane &l, int f)
 // few characters of text; over its FASTQ record (name + 2 L + 6 bytes) a record of L bases gains 52 + min(96, 4 L) - L / 2 <= 136 bytes.
 int64_t out_capacity(const kg_stream_config &cfg, int format)
 {
-	return 2 * cfg.max_window + (format == KG_STREAM_FORMAT_BAM ? 144 : 64) * cfg.max_reads + 4096;
+	return 2 * cfg.max_window + (format != KG_STREAM_FORMAT_SAM ? 144 : 64) * cfg.max_reads + 4096;
 }
 
 // A buffer that has to hold more: a new one of `bytes` in its place (nobody needs what the old one holds).  The caller synchronises the lane's
@@ -391,10 +407,43 @@ void kg_stream_close(kg_stream *s)
 	delete s;
 }
 
+// KG_STREAM_FORMAT_BAM_BGZF: room in the lane for `blocks` BGZF blocks that hold `bytes` of records -- a slot per block, the gathered members (a stored
+// member is its payload + 31 bytes) on the device, the tables, and a first page-locked buffer for the members.  Nothing of the lane's is in flight (the caller has synchronised).
+static int bgzf_room(kg_stream *s, Lane &l, int64_t blocks, int64_t bytes)
+{
+	if (!l.d_cuts) {
+		const size_t n = (size_t)s->cfg.max_reads + 8;
+		HIP_TRY(hipMalloc((void **)&l.d_cuts, 8 * n));
+		HIP_TRY(hipMalloc((void **)&l.d_range_first, 8 * n));
+		HIP_TRY(hipMalloc((void **)&l.d_bgzf_ctl, 8 * BGZ_WORDS));
+	}
+	if (blocks > l.bgzf_blocks) {
+		const int64_t want = blocks + blocks / 4 + 64;
+		const size_t scan_bytes = bgzf_scan_temp_bytes(std::max<int64_t>(s->cfg.max_reads + 8, want + 1));
+		l.bgzf_blocks = 0;
+		HIP_TRY(grow_device(l.d_block_src, 8 * (size_t)(want + 1)));
+		HIP_TRY(grow_device(l.d_block_off, 8 * (size_t)(want + 1)));
+		HIP_TRY(grow_device(l.d_block_bytes, 4 * (size_t)(want + 1)));
+		HIP_TRY(grow_device(l.d_slots, (size_t)(want * kBgzfSlot)));
+		HIP_TRY(grow_device(l.d_bgzf_scan, scan_bytes ? scan_bytes : 256));
+		HIP_TRY(grow_pinned(l.h_block_src, 8 * (size_t)(want + 1)));
+		HIP_TRY(grow_pinned(l.h_block_off, 8 * (size_t)(want + 1)));
+		l.bgzf_scan_bytes = scan_bytes;
+		l.bgzf_blocks = want;
+	}
+	const int64_t room = bytes + 31 * blocks;
+	if (room > l.d_bgzf_capacity) HIP_TRY(grow_device(l.d_bgzf, l.d_bgzf_capacity, room + room / 8, (size_t)(room + room / 8)));
+	// (page-locked memory is the dearer kind: half of that to begin with -- BAM records deflate to a quarter -- and map_copy_out grows it for a batch whose
+	//  blocks take more)
+	if (!l.h_bgzf) HIP_TRY(grow_pinned(l.h_bgzf, l.h_bgzf_capacity, room / 2 + 4096, (size_t)(room / 2 + 4096)));
+	return KG_OK;
+}
+
 int kg_stream_set_format(kg_stream *s, int format)
 {
 	if (!s) return fail(KG_ERR_ARG, "kg_stream_set_format: null stream");
-	if (format != KG_STREAM_FORMAT_SAM && format != KG_STREAM_FORMAT_BAM) return fail(KG_ERR_ARG, "kg_stream_set_format: unknown format %d (KG_STREAM_FORMAT_SAM or KG_STREAM_FORMAT_BAM)", format);
+	if (format != KG_STREAM_FORMAT_SAM && format != KG_STREAM_FORMAT_BAM && format != KG_STREAM_FORMAT_BAM_BGZF)
+		return fail(KG_ERR_ARG, "kg_stream_set_format: unknown format %d (KG_STREAM_FORMAT_SAM, KG_STREAM_FORMAT_BAM or KG_STREAM_FORMAT_BAM_BGZF)", format);
 	HIP_TRY(hipSetDevice(s->ix->device));
 	// the lanes' output buffers hold a batch in the larger of the two formats from the first BAM run on
 	const int64_t want = out_capacity(s->cfg, format);
@@ -406,6 +455,12 @@ int kg_stream_set_format(kg_stream *s, int format)
 		if (l.h_sam_capacity < want) {
 			HIP_TRY(hipStreamSynchronize(l.ws->stream));
 			HIP_TRY(grow_pinned(l.h_sam, l.h_sam_capacity, want, (size_t)want));
+		}
+		if (format == KG_STREAM_FORMAT_BAM_BGZF) {
+			// (chunks of ReadChunkSize = 4000 reads and a read in a hundred handed back: a batch that cuts its records finer grows the tables)
+			HIP_TRY(hipStreamSynchronize(l.ws->stream));
+			int rc = bgzf_room(s, l, bgzf_max_blocks(want, s->cfg.max_reads / 4000 + s->cfg.max_reads / 100 + 1), want);
+			if (rc != KG_OK) return rc;
 		}
 	}
 	s->format = format;
@@ -635,6 +690,7 @@ struct MapCall {
 	AlnArgs a;
 	SamArgs q;
 	bool checksum = false;
+	bool bgzf = false;                                 // the BGZF launch of the batch is on the lane's stream (KG_STREAM_FORMAT_BAM_BGZF)
 	int64_t sam_bytes = 0, n_host = 0, extra = 0;      // bytes of text, reads handed back, extra records of -m
 };
 
@@ -702,7 +758,7 @@ static int map_size_text(kg_stream *s, Lane &l, MapCall &m)
 	q.chr_names = s->d_chr_names; q.chr_name_off = s->d_chr_name_off;
 	q.sam_len = l.d_sam_len; q.sam_off = l.d_sam_off; q.sam = l.d_sam; q.sam_capacity = l.d_sam_capacity;
 	q.host_list = l.d_host_list; q.ctl = l.d_sam_ctl;
-	HIP_TRY(launch_text_size(q, s->format == KG_STREAM_FORMAT_BAM, l.d_scan, l.scan_bytes, s->ix->n_cu, st));
+	HIP_TRY(launch_text_size(q, s->format != KG_STREAM_FORMAT_SAM, l.d_scan, l.scan_bytes, s->ix->n_cu, st));
 	int64_t *word = l.h_meta + FQM_WORDS;
 	HIP_TRY(hipMemcpyAsync(&word[LW_TEXT_BYTES], l.d_sam_off + n, 8, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(&word[LW_HOST_READS], l.d_sam_ctl, 8, hipMemcpyDeviceToHost, st));
@@ -734,13 +790,42 @@ static int map_size_text(kg_stream *s, Lane &l, MapCall &m)
 	return KG_OK;
 }
 
+// KG_STREAM_FORMAT_BAM_BGZF: the records as BGZF blocks, cut where a chunk begins and where a read was handed back; the totals are on their way
+// to the lane's words when this returns (map_copy_out waits for them: the mode's one more sync)
+static int map_bgzf(kg_stream *s, Lane &l, MapCall &m)
+{
+	hipStream_t st = l.ws->stream;
+	const int64_t blocks = bgzf_max_blocks(m.sam_bytes, (int64_t)m.n_chunks + m.n_host + 1);
+	if (blocks > l.bgzf_blocks || m.sam_bytes + 31 * blocks > l.d_bgzf_capacity) {
+		HIP_TRY(kgi_sync(l.ws));
+		int rc = bgzf_room(s, l, blocks, m.sam_bytes);
+		if (rc != KG_OK) return rc;
+	}
+	BgzfArgs z{};
+	z.src = l.d_sam; z.src_bytes = m.sam_bytes;
+	z.cuts = l.d_cuts; z.n_cuts = m.n + 1;
+	z.max_blocks = l.bgzf_blocks;
+	z.range_first = l.d_range_first; z.block_src = l.d_block_src; z.block_bytes = l.d_block_bytes; z.block_off = l.d_block_off;
+	z.slots = l.d_slots; z.dst = l.d_bgzf; z.dst_capacity = l.d_bgzf_capacity; z.ctl = l.d_bgzf_ctl;
+	HIP_TRY(hipMemsetAsync(l.d_bgzf_ctl, 0, 8 * BGZ_WORDS, st));
+	HIP_TRY(launch_bgzf_stream_cuts(l.d_sam_off, m.n, l.win.chunk_reads > 0 ? l.win.chunk_reads : 1, l.d_cuts, l.d_bgzf_scan, l.bgzf_scan_bytes, s->ix->n_cu, st));
+	HIP_TRY(launch_bgzf(z, l.d_bgzf_scan, l.bgzf_scan_bytes, s->ix->n_cu, st));
+	HIP_TRY(hipMemcpyAsync(l.h_meta + FQM_WORDS + LW_BGZF, l.d_bgzf_ctl, 8 * BGZ_WORDS, hipMemcpyDeviceToHost, st));
+	m.bgzf = true;
+	return KG_OK;
+}
+
 static int map_format(kg_stream *s, Lane &l, MapCall &m)
 {
 	hipStream_t st = l.ws->stream;
-	HIP_TRY(launch_text_format(m.q, s->format == KG_STREAM_FORMAT_BAM, s->ix->n_cu, st));
+	HIP_TRY(launch_text_format(m.q, s->format != KG_STREAM_FORMAT_SAM, s->ix->n_cu, st));
 	// measurement aid (bench.py's gpu_pipeline leg): the text summed on the device, for runs that never copy it into file pages (read per call: a session switches it on and off)
 	m.checksum = getenv("KG_STREAM_CHECKSUM") != nullptr;
 	if (m.checksum) HIP_TRY(launch_sam_checksum(m.q, s->ix->n_cu, st));
+	if (s->format == KG_STREAM_FORMAT_BAM_BGZF) {
+		int rc = map_bgzf(s, l, m);
+		if (rc != KG_OK) return rc;
+	}
 	HIP_TRY(hipEventRecord(l.ev[5], st));
 	return KG_OK;
 }
@@ -753,6 +838,20 @@ static int map_copy_out(Lane &l, MapCall &m, kg_stream_result *out)
 	const int64_t n = m.n, n_host = m.n_host, extra = m.extra, *totals = m.totals;
 	const AlnArgs &a = m.a;
 	int64_t *word = l.h_meta + FQM_WORDS;
+	int64_t n_blocks = 0, bgzf_bytes = 0;
+	if (m.bgzf) {
+		// how many blocks and bytes the device made of the records: known once its kernels are through
+		HIP_TRY(kgi_sync(ws));
+		const int64_t *z = word + LW_BGZF;
+		n_blocks = z[BGZ_RUN]; bgzf_bytes = z[BGZ_BYTES];
+		if (z[BGZ_BLOCKS] != n_blocks || n_blocks > l.bgzf_blocks) return fail(KG_ERR_NO_DEVICE, "kg_stream_map: the records make %lld BGZF blocks, the lane was sized for %lld", (long long)z[BGZ_BLOCKS], (long long)l.bgzf_blocks);
+		if (z[BGZ_ERRORS] != 0) return fail(KG_ERR_NO_DEVICE, "kg_stream_map: %lld BGZF members missed the size computed for them", (long long)z[BGZ_ERRORS]);
+		if (bgzf_bytes > l.d_bgzf_capacity) return fail(KG_ERR_NO_DEVICE, "kg_stream_map: %lld bytes of BGZF blocks where at most %lld can be", (long long)bgzf_bytes, (long long)l.d_bgzf_capacity);
+		if (bgzf_bytes > l.h_bgzf_capacity) HIP_TRY(grow_pinned(l.h_bgzf, l.h_bgzf_capacity, bgzf_bytes + bgzf_bytes / 4, (size_t)(bgzf_bytes + bgzf_bytes / 4)));
+		if (bgzf_bytes > 0) HIP_TRY(hipMemcpyAsync(l.h_bgzf, l.d_bgzf, (size_t)bgzf_bytes, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(l.h_block_src, l.d_block_src, 8 * (size_t)(n_blocks + 1), hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(l.h_block_off, l.d_block_off, 8 * (size_t)(n_blocks + 1), hipMemcpyDeviceToHost, st));
+	}
 	if (m.sam_bytes > 0) HIP_TRY(hipMemcpyAsync(l.h_sam, l.d_sam, (size_t)m.sam_bytes, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(l.h_sam_off, l.d_sam_off, 8 * (size_t)(n + 1), hipMemcpyDeviceToHost, st));
 	// the records, candidate offsets, candidates and their seeds stay on the device unless the caller wants them all: it asks for the chunks it needs
@@ -785,6 +884,10 @@ static int map_copy_out(Lane &l, MapCall &m, kg_stream_result *out)
 	out->host_reads = l.h_host_list; out->n_host_reads = n_host;
 	out->cand_off = l.h_cand_off; out->cands = l.h_cands; out->cand_seeds = l.h_cand_seeds;
 	out->rec_start[0] = l.h_rec_hdr[0]; out->rec_start[1] = l.win.two_files ? l.h_rec_hdr[1] : nullptr;
+	if (m.bgzf) {
+		out->bgzf = l.h_bgzf; out->bgzf_bytes = bgzf_bytes; out->n_blocks = n_blocks;
+		out->block_src = l.h_block_src; out->block_off = l.h_block_off;
+	}
 	l.have_batch = false;
 	return KG_OK;
 }

@@ -125,6 +125,7 @@ int kh_map(kh_session *s, int argc, const char *const *argv, kh_stats_t *stats)
 		for (int i = 0; i < 6; ++i) stats->lane_seconds[i] = st.lane_seconds[i];
 		stats->lanes = st.lanes; stats->pad2 = 0;
 		stats->text_checksum[0] = st.device.text_checksum[0]; stats->text_checksum[1] = st.device.text_checksum[1];
+		stats->bgzf_device_bytes = st.bgzf_device_bytes; stats->bgzf_host_bytes = st.bgzf_host_bytes;
 	}
 	if (rc == 0) return 0;
 	const std::string why = kart::run_error_message();

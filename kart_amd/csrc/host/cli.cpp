@@ -29,6 +29,7 @@ static void usage(const char *prog)
 	fprintf(stdout, "         -f2           files with #2 mates reads (format:fa, fq, fq.gz)\n");
 	fprintf(stdout, "         -o            alignment filename in SAM format [output.sam]\n");
 	fprintf(stdout, "         -bo           alignment filename in BAM format\n");
+	fprintf(stdout, "         -bz STR       with -bo: who compresses the BAM records, host (zlib) or device [host]\n");
 	fprintf(stdout, "         -m            output multiple alignments\n");
 	fprintf(stdout, "         -g INT        max gaps (indels) [5]\n");
 	fprintf(stdout, "         -p            paired-end reads are interlaced in the same file\n");
@@ -60,6 +61,15 @@ int parse_cli(int argc, char **argv, Options &opt)
 			if ((opt.max_gaps = atoi(argv[++i])) < 0) opt.max_gaps = 0;
 		} else if (p == "-o" && i + 1 < argc) { opt.bam = false; opt.out_name = argv[++i]; }
 		else if (p == "-bo" && i + 1 < argc) { opt.bam = true; opt.out_name = argv[++i]; }
+		else if (p == "-bz") {                           // (a flag, not an environment knob: it changes the file's bytes -- never its content)
+			const std::string v = i + 1 < argc ? argv[++i] : "";
+			if (v != "host" && v != "device") {
+				fprintf(stdout, "Error! -bz expects host or device\n");
+				usage(argv[0]);
+				return -2;
+			}
+			opt.bz_device = v == "device";
+		}
 		else if (p == "-gpu" && i + 1 < argc) {          // one device, or a list a,b,c: one process per device, the input sharded
 			opt.devices.clear();
 			for (const char *q = argv[++i]; *q;) {
@@ -227,6 +237,7 @@ int cli_main(int argc, char **argv, KernelBackend *(*make_backend)(const Options
 		fprintf(stdout, "Alignment output: %s\n", opt.out_name.c_str());
 		if (getenv("KART_AMD_VERBOSE") && !launcher) fprintf(stdout, "mapping seconds (index load excluded): %.3f\n", st.map_seconds);
 		if (getenv("KART_AMD_VERBOSE")) fprintf(stdout, "chunks re-mapped after EstDistance speculation: %lld\n", (long long)st.respeculated);
+		if (getenv("KART_AMD_VERBOSE") && opt.bam) fprintf(stdout, "device deflate: %lld of %lld bytes\n", (long long)st.bgzf_device_bytes, (long long)(st.bgzf_device_bytes + st.bgzf_host_bytes));
 	}
 	return 0;
 }

@@ -219,7 +219,9 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 	// ... and gz libraries: their text is inflated by threads of their own into a growing block that the stream reads like a mapped file
 	// (Source::gz_stream_begin; KART_AMD_NO_GZ_STREAM: the host's gz reader maps them, as until round 5)
 	// -bo: the device makes the BAM records (kg_stream_set_format) and the committed chunks are compressed beside the commit (BamPacker); a sharded
-	// -bo run keeps the host's reader and encoder (a deferred shard holds text it may have to map again)
+	// -bo run keeps the host's reader and encoder (a deferred shard holds text it may have to map again).  -bz device: the device compresses the records
+	// as well (KG_STREAM_FORMAT_BAM_BGZF) and the packer takes its blocks where a piece of a chunk is made of whole ones; whatever does not go through
+	// the stream -- a sharded run, -pacbio, KART_AMD_NO_STREAM, what the reader below maps after the stream stopped -- is compressed by the host as ever
 	const bool bam_by_host = cx.opt.bam && shard.active();
 	// FASTA (kg_stream_set_input): plain files mapped for the stream (Source::fasta_fast) and gz alike; a sharded run keeps the general reader
 	if (src.gzfast && !src.fast && !cx.opt.pacbio && !g_check_align && cx.kern.has_stream() && !getenv("KART_AMD_NO_GZ_STREAM") && !shard.active()) src.gz_stream_begin();
@@ -263,7 +265,7 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 		int lanes = lanes_env > 0 ? std::min(lanes_env, 16) : (group ? 2 * group : 4);      // (independent lanes, six writers: 3 lanes 0.75-0.79 s per 20 M reads, 4 0.73 s, 5 0.72-0.73 s)
 		if (group && lanes % group != 0) lanes = (lanes + group - 1) / group * group;
 		if (StreamBackend *sb = cx.kern.stream(full_reads + full_reads / 4 + chunk_limit, window, lanes, group)) {
-			sb->set_format(cx.opt.bam);                 // (the stream is the session's: a -o run may follow a -bo run)
+			sb->set_format(cx.opt.bam, cx.opt.bam && cx.opt.bz_device);      // (the stream is the session's: a -o run may follow a -bo run, a -bz host run a -bz device one)
 			sb->set_input(!cx.fastq);                   // (... and a FASTQ library a FASTA one)
 			Options &o = const_cast<Options &>(cx.opt);
 			const int64_t keep = o.batch_reads;

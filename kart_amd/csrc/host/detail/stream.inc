@@ -96,12 +96,34 @@ private:
 	bool stop_ = false;
 };
 
+// The BGZF blocks the device made of a batch's records (kg_stream_result::block_src, n_blocks + 1 ascending offsets into the records) that hold exactly
+// the bytes [from, to) of them: blocks [first, last), `whole` where both ends are block boundaries.  The device cuts at every chunk's first byte and at
+// the place of every read it handed back, so a piece of a chunk between two such places is whole; a piece next to a pair the commit mapped again
+// under another EstDistance ends inside a block and is not.
+struct BlockRange {
+	int64_t first = 0, last = 0;
+	bool whole = false;
+};
+inline BlockRange stream_piece_blocks(const int64_t *block_src, int64_t n_blocks, int64_t from, int64_t to)
+{
+	BlockRange r;
+	if (!block_src || n_blocks <= 0 || to <= from) return r;
+	const int64_t *end = block_src + n_blocks + 1;
+	const int64_t *a = std::lower_bound(block_src, end, from), *b = std::lower_bound(a, end, to);
+	r.first = a - block_src; r.last = b - block_src;
+	r.whole = a != end && b != end && *a == from && *b == to;
+	return r;
+}
+
 // -bo: the committed chunks of a run whose records the device makes as BAM (kg_stream_set_format).  A chunk's raw BAM is its pieces joined -- the
 // device's records out of the lane's buffer, the host's own records (bam_raw_pieces) between them -- and is compressed as one series of BGZF blocks
 // per chunk: what bam_encode_chunk makes of the same chunk's text on the host's path, so the file is the same byte for byte.  Deflate is the run's
 // largest cost on the host, so it runs on threads of its own beside the commit.  The file's order is the chunks' order, and a chunk's place in the
 // file is known only once every chunk before it has been compressed: whoever finishes the next chunk in line hands it -- and the finished ones
 // behind it -- to the writer.
+// -bz device (KG_STREAM_FORMAT_BAM_BGZF): the batch comes with the BGZF blocks the device made of its records.  A device piece whose two ends are
+// block boundaries (stream_piece_blocks) goes into the file as those blocks, unchanged; everything else -- the host's own records, a device piece
+// next to a pair that was mapped again -- is compressed here as before, neighbouring such pieces together.  The inflated stream is the same.
 class BamPacker {
 public:
 	BamPacker(Writer *writer, int n_threads, std::mutex *done_mu, std::condition_variable *done_cv) : writer_(writer), done_mu_(done_mu), done_cv_(done_cv)
@@ -110,12 +132,14 @@ public:
 	}
 	~BamPacker() { finish(); }
 	// the pieces stay where they are until *pending has been decremented (under *done_mu): the lane's buffers are free again once the chunk is joined
-	void push(std::vector<TextPiece> &&pieces, size_t total, std::string &&hold, std::atomic<int> *pending)
+	// res: the batch's result where it carries the device's BGZF blocks (else null); it is the lane's, as the pieces are
+	void push(std::vector<TextPiece> &&pieces, size_t total, std::string &&hold, std::atomic<int> *pending, const kg_stream_result *res = nullptr)
 	{
 		std::lock_guard<std::mutex> lk(mu_);
 		q_.emplace_back();
 		Job &j = q_.back();
 		j.seq = pushed_++; j.pieces = std::move(pieces); j.total = total; j.hold = std::move(hold); j.pending = pending;
+		j.res = res && res->n_blocks > 0 ? res : nullptr;
 		cv_.notify_one();
 	}
 	// every chunk pushed so far is with the writer when this returns
@@ -130,6 +154,8 @@ public:
 		th_.clear();
 	}
 	int64_t bytes() const { return bytes_; }
+	int64_t device_bytes() const { return device_bytes_; }     // file bytes the device compressed / the host did (after finish())
+	int64_t host_bytes() const { return bytes_ - device_bytes_; }
 
 private:
 	struct Job {
@@ -138,6 +164,12 @@ private:
 		size_t total = 0;
 		std::string hold;
 		std::atomic<int> *pending = nullptr;
+		const kg_stream_result *res = nullptr;
+	};
+	// a run of the chunk: BGZF blocks of the device's, or raw records the host compresses
+	struct Seg {
+		bool packed = false;
+		std::string bytes;
 	};
 	void loop()
 	{
@@ -150,21 +182,41 @@ private:
 				j = std::move(q_.front());
 				q_.pop_front();
 			}
-			std::string raw, out;
-			raw.reserve(j.total);
-			size_t hold_at = 0;
+			std::string out;
+			std::vector<Seg> segs;
+			size_t hold_at = 0, raw_bytes = 0;
 			for (const TextPiece &tp : j.pieces) {
-				if (tp.p) raw.append(tp.p, tp.n);
-				else { raw.append(j.hold.data() + hold_at, tp.n); hold_at += tp.n; }
+				BlockRange br;
+				if (tp.p && j.res) br = stream_piece_blocks(j.res->block_src, j.res->n_blocks, tp.p - j.res->sam, tp.p - j.res->sam + (int64_t)tp.n);
+				if (br.whole) {
+					const int64_t *off = j.res->block_off;
+					segs.emplace_back();
+					segs.back().packed = true;
+					segs.back().bytes.assign((const char *)j.res->bgzf + off[br.first], (size_t)(off[br.last] - off[br.first]));
+					continue;
+				}
+				if (segs.empty() || segs.back().packed) {
+					segs.emplace_back();
+					if (!j.res) segs.back().bytes.reserve(j.total);
+				}
+				if (tp.p) segs.back().bytes.append(tp.p, tp.n);
+				else { segs.back().bytes.append(j.hold.data() + hold_at, tp.n); hold_at += tp.n; }
+				raw_bytes += tp.n;
 			}
 			{
 				std::lock_guard<std::mutex> lk(*done_mu_);
 				j.pending->fetch_sub(1);
 				done_cv_->notify_all();
 			}
-			out.reserve(raw.size() / 3 + 64);
-			bgzf_append(raw, out);
+			size_t packed_bytes = 0;
+			for (const Seg &sg : segs) packed_bytes += sg.packed ? sg.bytes.size() : 0;
+			out.reserve(packed_bytes + raw_bytes / 3 + 64);
+			for (const Seg &sg : segs) {
+				if (sg.packed) out.append(sg.bytes);
+				else bgzf_append(sg.bytes, out);
+			}
 			std::lock_guard<std::mutex> lk(mu_);
+			device_bytes_ += (int64_t)packed_bytes;
 			ready_[j.seq] = std::move(out);
 			for (std::map<int64_t, std::string>::iterator it = ready_.begin(); it != ready_.end() && it->first == next_; it = ready_.erase(it), ++next_) {
 				bytes_ += (int64_t)it->second.size();
@@ -179,7 +231,7 @@ private:
 	std::condition_variable cv_;
 	std::deque<Job> q_;
 	std::map<int64_t, std::string> ready_;      // compressed chunks that wait for one before them
-	int64_t pushed_ = 0, next_ = 0, bytes_ = 0;
+	int64_t pushed_ = 0, next_ = 0, bytes_ = 0, device_bytes_ = 0;
 	bool stop_ = false;
 	std::vector<std::thread> th_;
 };
@@ -860,7 +912,7 @@ struct StreamRun {
 			st.total_reads += ck.count;
 			st.unmapped += ck.st.unmapped;
 			st.unique += ck.st.unique;
-			if (packer) packer->push(std::move(pieces), total, std::move(ck.text), &b.writes_pending);
+			if (packer) packer->push(std::move(pieces), total, std::move(ck.text), &b.writes_pending, &b.res);
 			else writer->push_pieces(std::move(pieces), total, std::move(ck.text), &b.writes_pending, &feed.mu, &feed.cv);
 		}
 	}
@@ -891,6 +943,7 @@ struct StreamRun {
 	{
 		feed.wait_writes_done(batches);
 		if (packer) packer->finish();              // (the caller's own reader and writer may continue behind the stream's last chunk)
+		if (packer) { st.bgzf_device_bytes += packer->device_bytes(); st.bgzf_host_bytes += packer->host_bytes(); }
 		src.m1.pos = feed.pos[0];
 		if (src.sep) src.m2.pos = feed.pos[1];
 	}

@@ -66,9 +66,9 @@ public:
 	{
 		if (kg_stream_group_absent(s_, lane, rounds) != KG_OK) die("kg_stream_group_absent");
 	}
-	void set_format(bool bam) override
+	void set_format(bool bam, bool bgzf) override
 	{
-		if (kg_stream_set_format(s_, bam ? KG_STREAM_FORMAT_BAM : KG_STREAM_FORMAT_SAM) != KG_OK) die("kg_stream_set_format");
+		if (kg_stream_set_format(s_, !bam ? KG_STREAM_FORMAT_SAM : bgzf ? KG_STREAM_FORMAT_BAM_BGZF : KG_STREAM_FORMAT_BAM) != KG_OK) die("kg_stream_set_format");
 	}
 	void set_input(bool fasta) override
 	{

@@ -35,6 +35,7 @@ struct Options {
 	bool multi_hit = false;   // -m
 	bool silent = false;      // -silent
 	bool bam = false;         // -bo: BAM instead of SAM (src/main.cpp:155-158)
+	bool bz_device = false;   // -bz device: the BGZF blocks of a -bo run that goes through the stream are compressed on the device (default: host, zlib)
 	int device = 0;
 	std::vector<int> devices;       // -gpu a,b,c: one process per listed device, the input sharded between them
 	int shard_rank = 0, shard_count = 1;   // this process maps shard_rank of shard_count contiguous chunk ranges of the library ...
@@ -92,7 +93,8 @@ struct StreamBackend {
 	virtual int seed_group() const { return 0; }
 	virtual void group_absent(int lane, int rounds) { (void)lane; (void)rounds; }
 	// what map() leaves in the result's sam / sam_off from here on: SAM lines, or (bam) uncompressed BAM records (kg_stream_set_format); while no lane works
-	virtual void set_format(bool bam) { (void)bam; }
+	// bgzf (with bam): the result carries the BGZF blocks of the records as well (KG_STREAM_FORMAT_BAM_BGZF)
+	virtual void set_format(bool bam, bool bgzf = false) { (void)bam; (void)bgzf; }
 	// what parse() takes the text for from here on: 4-line FASTQ, or (fasta) FASTA records (kg_stream_set_input); while no lane works
 	virtual void set_input(bool fasta) { (void)fasta; }
 };
@@ -196,6 +198,7 @@ struct Stats {
 	int64_t respeculated = 0;   // chunks re-mapped because their speculated EstDistance did not hold
 	int64_t rewritten_chunks = 0;   // (-parts, a later shard) chunks whose text was written a second time because settling changed a chunk in front of them
 	int64_t stream_reads = 0;   // reads that went through the device's FASTQ-in / SAM-out stream
+	int64_t bgzf_device_bytes = 0, bgzf_host_bytes = 0;   // -bo through the stream: file bytes of its chunks that the device compressed (-bz device) / the host's zlib did
 	kg_stream_timing_t device{};   // ... and what their batches cost on the device (HIP events on the lanes' streams, summed)
 	double lane_seconds[6] = {0, 0, 0, 0, 0, 0};   // ... and what the lanes' host threads waited for / worked on (kh_stats_t::lane_seconds), summed over `lanes` threads
 	int lanes = 0;
