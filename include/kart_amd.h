@@ -333,6 +333,35 @@ int  kg_fragments_batch(kg_index *ix, const char *frag1, const int64_t *off1, co
 int  kg_bgzf_deflate(int device, const uint8_t *src, int64_t src_bytes, const int64_t *cuts, int64_t n_cuts,
                      uint8_t *dst, int64_t dst_capacity, int64_t *block_src, int64_t *block_off, int64_t max_blocks, int64_t *n_blocks);
 
+/* ---- BGZF members in, their text out --------------------------------------------------------------------------------------- */
+/* The mirror of kg_bgzf_deflate: n_members gzip members as bgzip makes them, member i = src[member_off[i], member_off[i+1]), inflated on the device
+ * (RFC 1951: stored, fixed and dynamic blocks, any number per member) to dst[text_off[i], text_off[i+1]).  The device finds the deflate stream itself
+ * (12 + XLEN bytes in) and holds every member to what gzread() holds it to: the stream ends with a final block exactly 8 bytes in front of the member's
+ * end, it made exactly ISIZE = text_off[i+1] - text_off[i] bytes, and their CRC-32 is the trailer's.  status[i] says which of these failed; a bad
+ * member is not a failed call (KG_OK), the other members are inflated as usual, and no byte outside a member's own ranges is read or written
+ * whatever its stream says.  Offsets that do not ascend, member_off[n_members] != src_bytes, text_off[0] != 0, a member or a text piece longer than
+ * 65536 bytes: KG_ERR_ARG; text_off[n_members] > dst_capacity: KG_ERR_CAPACITY.  n_members == 0 and members of no text (the EOF block) are legal. */
+#define KG_INFLATE_OK      0
+#define KG_INFLATE_HEADER  1   /* not a gzip member with an extra field, or shorter than 12 + XLEN + 8 */
+#define KG_INFLATE_STREAM  2   /* the deflate stream is at fault, ends early or ends late */
+#define KG_INFLATE_SIZE    3   /* ISIZE is not the text piece's size, or the stream makes more or less */
+#define KG_INFLATE_CRC     4
+/* one shot, host pointers, copies in and out */
+int  kg_bgzf_inflate(int device, const uint8_t *src, int64_t src_bytes, const int64_t *member_off, const int64_t *text_off,
+                     int64_t n_members, uint8_t *dst, int64_t dst_capacity, int32_t *status);
+/* For a caller that inflates round after round: page-locked buffers and a HIP stream of its own (not the null stream: nothing else waits for it).
+ * max_* size the first buffers; kg_inflater_reserve() makes them hold a larger round (the source buffer may move: what it held is kept, ask kg_inflater_src() again), and a run that
+ * exceeds them is KG_ERR_CAPACITY.  The caller reads the members straight into kg_inflater_src(k) and runs them; *text (the members' text, back to
+ * back along text_off) and *status are page-locked and the inflater's, valid until the next run or reserve.  *device_ms (may be null): the launch as
+ * HIP events around it timed it. */
+typedef struct kg_inflater kg_inflater;
+int  kg_inflater_create(int device, int64_t max_src_bytes, int64_t max_text_bytes, int64_t max_members, kg_inflater **out);
+int  kg_inflater_reserve(kg_inflater *k, int64_t src_bytes, int64_t text_bytes, int64_t members);
+uint8_t *kg_inflater_src(kg_inflater *k);
+int  kg_inflater_run(kg_inflater *k, int64_t src_bytes, const int64_t *member_off, const int64_t *text_off, int64_t n_members,
+                     const uint8_t **text, const int32_t **status, double *device_ms);
+void kg_inflater_destroy(kg_inflater *k);
+
 /* ---- FASTQ text in, SAM text (or BAM records) out ------------------------------------------------------------------- */
 /* The reference's worker takes a chunk of reads from GetNextChunk (src/GetData.cpp:109-143: four getline() calls per record,
  * the name cut out of the header by IdentifyHeaderBegPos / EndPos, mate 2 reverse-complemented), maps it, and prints every

@@ -60,6 +60,11 @@ typedef struct {
 	/* -bo through the device stream: bytes of the BGZF blocks of its chunks in the file that the device compressed (-bz device) and that the host's zlib
 	 * did (the header, the end-of-file block and what the general reader maps are the host's always and are not counted) */
 	int64_t bgzf_device_bytes, bgzf_host_bytes;
+	/* bgzip-ped read files: bytes of text of their BGZF members that the device inflated (-fz device) and that the host's zlib did (ordinary gzip and
+	 * whatever gzread() finished behind a damaged or foreign member are not counted), and the device's time for its share (HIP events around the
+	 * launches, summed) */
+	int64_t inflate_device_bytes, inflate_host_bytes;
+	double  inflate_device_ms;
 } kh_stats_t;
 
 const char *kh_last_error(void);
@@ -69,8 +74,9 @@ const char *kh_last_error(void);
 int  kh_open(const char *index_prefix, int device, int threads, kh_session **out);
 
 /* One mapping run.  argv holds the reference's command-line flags for the run (src/main.cpp:123-176): -f <files> [-f2
- * <files>] -o|-bo <out> [-m] [-p] [-pacbio] [-g INT] [-silent], plus this pipeline's -shard r/N -rendezvous FILE; -i, -t and
- * -gpu are fixed by the session.  Returns 0 on success. */
+ * <files>] -o|-bo <out> [-m] [-p] [-pacbio] [-g INT] [-silent], plus this pipeline's -shard r/N -rendezvous FILE, -bz host|device (who compresses
+ * a -bo run's blocks) and -fz host|device (who inflates bgzip-ped read files: zlib on the session's threads, or the device; the output is the same);
+ * -i, -t and -gpu are fixed by the session.  Returns 0 on success. */
 int  kh_map(kh_session *s, int argc, const char *const *argv, kh_stats_t *stats);
 /* (measurement aid: with KART_AMD_OUTPUT_NULL=1 in the environment of a kh_map call the text goes to /dev/null instead of the file named by
  *  -o -- everything up to the host's copy into the file's pages runs as usual; bench.py's gpu_pipeline leg) */

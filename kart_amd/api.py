@@ -56,7 +56,7 @@ ABI_SYMBOLS = (
     "kg_fragments_batch", "kg_longread_batch", "kg_longread_reasons",
     "kg_stream_open", "kg_stream_close", "kg_stream_staging", "kg_stream_upload", "kg_stream_parse", "kg_stream_map", "kg_stream_fetch", "kg_stream_fetch_reads", "kg_stream_timing",
     "kg_stream_group_absent", "kg_stream_group_abort", "kg_stream_set_format", "kg_stream_set_input",
-    "kg_bgzf_deflate",
+    "kg_bgzf_deflate", "kg_bgzf_inflate", "kg_inflater_create", "kg_inflater_reserve", "kg_inflater_src", "kg_inflater_run", "kg_inflater_destroy",
 )
 
 
@@ -228,6 +228,14 @@ def load_library() -> C.CDLL:
     L.kg_stream_set_input.argtypes = [C.c_void_p, C.c_int]
     L.kg_stream_timing.argtypes = [C.c_void_p, C.POINTER(StreamTiming), C.c_int]
     L.kg_bgzf_deflate.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+    L.kg_bgzf_inflate.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    L.kg_inflater_create.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]
+    L.kg_inflater_reserve.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64]
+    L.kg_inflater_src.argtypes = [C.c_void_p]
+    L.kg_inflater_src.restype = C.c_void_p
+    L.kg_inflater_run.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_double)]
+    L.kg_inflater_destroy.argtypes = [C.c_void_p]
+    L.kg_inflater_destroy.restype = None
     _lib = L
     return L
 
@@ -265,6 +273,91 @@ def bgzf_deflate(data: bytes, cuts=None, device: int = 0, dst_capacity: int | No
     _check(load_library().kg_bgzf_deflate(device, _ptr(src), len(data), _ptr(cuts), len(cuts), _ptr(dst), dst_capacity, _ptr(block_src), _ptr(block_off),
                                           max_blocks, C.byref(n)), "kg_bgzf_deflate")
     return dst[:int(block_off[n.value])].tobytes(), block_src[:n.value + 1].copy(), block_off[:n.value + 1].copy()
+
+
+KG_INFLATE_OK, KG_INFLATE_HEADER, KG_INFLATE_STREAM, KG_INFLATE_SIZE, KG_INFLATE_CRC = 0, 1, 2, 3, 4
+BGZF_MEMBER_MAX = 65536                # bytes of a BGZF member, and of its text, at most
+
+
+def bgzf_members(data: bytes):
+    """The member table of a BGZF file from a walk along BSIZE (the 'BC' extra subfield) and ISIZE (a member's last four bytes) -> (member_off,
+    text_off).  An ISIZE above 64 KiB -- no BGZF member has one -- gets a text piece of no bytes, which the device then refuses as KG_INFLATE_SIZE."""
+    member_off, text_off, at = [0], [0], 0
+    while at < len(data):
+        size = 0
+        if len(data) - at >= 18 and data[at:at + 2] == b"\x1f\x8b":
+            xlen = int.from_bytes(data[at + 10:at + 12], "little")
+            x = at + 12
+            while x + 6 <= min(at + 12 + xlen, len(data)):
+                slen = int.from_bytes(data[x + 2:x + 4], "little")
+                if data[x:x + 2] == b"BC" and slen == 2:
+                    size = int.from_bytes(data[x + 4:x + 6], "little") + 1
+                    break
+                x += 4 + slen
+        if size < 8 or at + size > len(data):
+            raise KartAmdError(f"no whole BGZF member at byte {at}")
+        isize = int.from_bytes(data[at + size - 4:at + size], "little")
+        at += size
+        member_off.append(at)
+        text_off.append(text_off[-1] + (isize if isize <= BGZF_MEMBER_MAX else 0))
+    return np.asarray(member_off, dtype=np.int64), np.asarray(text_off, dtype=np.int64)
+
+
+def bgzf_inflate(data: bytes, member_off=None, text_off=None, device: int = 0, dst_capacity: int | None = None):
+    """kg_bgzf_inflate: the BGZF members of `data` inflated on the device -> (text, text_off, status).  Member i is data[member_off[i]:
+    member_off[i+1]] and becomes text[text_off[i]:text_off[i+1]]; status[i] is KG_INFLATE_* (a refused member's piece of the text is zeros).  Without a
+    table the offsets come from bgzf_members(); with member_off alone, text_off is every member's ISIZE."""
+    if member_off is None:
+        member_off, text_off = bgzf_members(data)
+    member_off = np.ascontiguousarray(member_off, dtype=np.int64)
+    if text_off is None:
+        sizes = [int.from_bytes(data[e - 4:e], "little") if e >= 4 else 0 for e in member_off[1:].tolist()]
+        text_off = np.concatenate([[0], np.cumsum([s if s <= BGZF_MEMBER_MAX else 0 for s in sizes], dtype=np.int64)])
+    text_off = np.ascontiguousarray(text_off, dtype=np.int64)
+    if len(member_off) < 1 or len(member_off) != len(text_off):
+        raise KartAmdError("bgzf_inflate: member_off and text_off are tables of n + 1 offsets each")
+    n = len(member_off) - 1
+    dst_capacity = int(text_off[-1]) if dst_capacity is None else int(dst_capacity)
+    src = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(1, dtype=np.uint8)
+    dst = np.zeros(max(1, dst_capacity), dtype=np.uint8)
+    status = np.full(max(1, n), -1, dtype=np.int32)
+    _check(load_library().kg_bgzf_inflate(device, _ptr(src), len(data), _ptr(member_off), _ptr(text_off), n, _ptr(dst), dst_capacity, _ptr(status)),
+           "kg_bgzf_inflate")
+    return dst[:int(text_off[-1])].tobytes(), text_off.copy(), status[:n].copy()
+
+
+class Inflater:
+    """kg_inflater_*: page-locked buffers and a HIP stream of their own, for round after round of members."""
+
+    def __init__(self, max_src_bytes: int, max_text_bytes: int, max_members: int, device: int = 0):
+        self.lib = load_library()
+        h = C.c_void_p()
+        _check(self.lib.kg_inflater_create(device, max_src_bytes, max_text_bytes, max_members, C.byref(h)), "kg_inflater_create")
+        self.h = h
+        self.src_room = max_src_bytes                  # what the source buffer holds at least
+
+    def reserve(self, src_bytes: int, text_bytes: int, members: int):
+        _check(self.lib.kg_inflater_reserve(self.h, src_bytes, text_bytes, members), "kg_inflater_reserve")
+        self.src_room = max(self.src_room, src_bytes)
+
+    def run(self, data: bytes, member_off, text_off):
+        """-> (text, status, device_ms); `data` is copied into the inflater's source buffer as a caller's pread() would fill it"""
+        member_off = np.ascontiguousarray(member_off, dtype=np.int64)
+        text_off = np.ascontiguousarray(text_off, dtype=np.int64)
+        n = len(member_off) - 1
+        src = self.lib.kg_inflater_src(self.h)
+        if 0 < len(data) <= self.src_room and src:     # (more than the buffer holds: nothing is copied, the run says KG_ERR_CAPACITY)
+            C.memmove(src, data, len(data))
+        text, status, ms = C.c_void_p(), C.c_void_p(), C.c_double()
+        _check(self.lib.kg_inflater_run(self.h, len(data), _ptr(member_off), _ptr(text_off), n, C.byref(text), C.byref(status), C.byref(ms)), "kg_inflater_run")
+        out = C.string_at(text, int(text_off[-1])) if n and text_off[-1] else b""
+        st = np.frombuffer(C.string_at(status, 4 * n), dtype=np.int32).copy() if n else np.zeros(0, dtype=np.int32)
+        return out, st, ms.value
+
+    def close(self):
+        if self.h:
+            self.lib.kg_inflater_destroy(self.h)
+            self.h = None
 
 
 def concat_reads(reads):
@@ -642,7 +735,8 @@ class HostStats(C.Structure):
                 ("search_kernel_launches", C.c_int64), ("search_useful_bytes", C.c_double), ("text_in_bytes", C.c_double), ("text_out_bytes", C.c_double),
                 ("candidates", C.c_double), ("candidate_seeds", C.c_double), ("kernel_ms", C.c_double * 16), ("kernel_launches", C.c_int64 * 16), ("aln_counts", C.c_double * 8),
                 ("lane_seconds", C.c_double * 6), ("lanes", C.c_int32), ("pad2", C.c_int32), ("text_checksum", C.c_double * 2),
-                ("bgzf_device_bytes", C.c_int64), ("bgzf_host_bytes", C.c_int64)]
+                ("bgzf_device_bytes", C.c_int64), ("bgzf_host_bytes", C.c_int64),
+                ("inflate_device_bytes", C.c_int64), ("inflate_host_bytes", C.c_int64), ("inflate_device_ms", C.c_double)]
 
     def as_dict(self):
         return {n: (list(getattr(self, n)) if n.startswith(("kernel_", "stage_", "aln_counts")) else getattr(self, n)) for n, _ in self._fields_}

@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "kernels/bgzf_block.inc"
+#include "kernels/bgzf_inflate.inc"
 
 namespace kg {
 
@@ -107,6 +108,21 @@ __global__ __launch_bounds__(256) void bgzf_stream_cuts_kernel(const int64_t *sa
 	}
 }
 
+// ---- inflate -------------------------------------------------------------------------------------------------------------------
+// one wave per member at a time: a workgroup IS a wave, so that its barriers are fences, and ~8 KiB of LDS let sixteen of them share a CU
+__global__ __launch_bounds__(bgzf::kWave) void bgzf_inflate_kernel(BgzfInflateArgs a)
+{
+	__shared__ bgzf::InflateShared sh;
+	for (int64_t i = blockIdx.x; i < a.n_members; i += gridDim.x) {
+		const int64_t m0 = a.member_off[i], m1 = a.member_off[i + 1], t0 = a.text_off[i], t1 = a.text_off[i + 1];
+		int status;
+		if (m0 < 0 || m1 < m0 || m1 > a.src_bytes || m1 - m0 > kBgzfSlot) status = bgzf::kInflateHeader;
+		else if (t0 < 0 || t1 < t0 || t1 > a.dst_capacity || t1 - t0 > kBgzfSlot) status = bgzf::kInflateSize;
+		else status = bgzf::inflate_member(sh, a.src + m0, (int)(m1 - m0), a.dst + t0, (int)(t1 - t0));
+		if (threadIdx.x == 0) a.status[i] = status;
+	}
+}
+
 size_t bgzf_scan_temp_bytes(int64_t max_items)
 {
 	size_t b1 = 0, b2 = 0, b3 = 0;
@@ -133,6 +149,14 @@ hipError_t launch_bgzf(const BgzfArgs &a, void *scan_temp, size_t scan_temp_byte
 	if (e != hipSuccess) return e;
 	hipLaunchKernelGGL(bgzf_pack_kernel, dim3(grid_of(a.max_blocks, 1, n_cu * 8)), dim3(256), 0, stream, a);
 	kt_end(KT_BGZF, stream);
+	return hipGetLastError();
+}
+
+hipError_t launch_bgzf_inflate(const BgzfInflateArgs &a, int n_cu, hipStream_t stream)
+{
+	if (a.n_members < 0) return hipErrorInvalidValue;
+	if (a.n_members == 0) return hipSuccess;
+	hipLaunchKernelGGL(bgzf_inflate_kernel, dim3(grid_of(a.n_members, 1, n_cu * 16)), dim3(bgzf::kWave), 0, stream, a);
 	return hipGetLastError();
 }
 

@@ -42,4 +42,21 @@ hipError_t launch_bgzf(const BgzfArgs &a, void *scan_temp, size_t scan_temp_byte
 // last read at or in front of r that begins a chunk of chunk_reads reads or was handed back (sam_off[r] == sam_off[r + 1]); cuts[n_reads] = the end
 hipError_t launch_bgzf_stream_cuts(const int64_t *sam_off, int64_t n_reads, int chunk_reads, int64_t *cuts, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream);
 
+// ---- the other way: BGZF members inflated on the device (kernels/bgzf_inflate.inc) ---------------------------------------------
+// Member i is src[member_off[i], member_off[i + 1]) and becomes dst[text_off[i], text_off[i + 1]): one wave per member, which finds the deflate
+// stream behind the member's gzip header itself and checks the trailer's CRC-32 and ISIZE.  status[i] is KG_INFLATE_* (include/kart_amd.h); a member
+// whose ranges do not lie inside src / dst, or are longer than 64 KiB, is refused without a byte of it being read.
+struct BgzfInflateArgs {
+	const uint8_t *src;
+	int64_t src_bytes;
+	const int64_t *member_off;     // [n_members + 1]
+	const int64_t *text_off;       // [n_members + 1]
+	int64_t n_members;
+	uint8_t *dst;
+	int64_t dst_capacity;
+	int32_t *status;               // [n_members]
+};
+// everything on `stream`, no synchronisation
+hipError_t launch_bgzf_inflate(const BgzfInflateArgs &a, int n_cu, hipStream_t stream);
+
 }  // namespace kg

@@ -30,6 +30,7 @@ static void usage(const char *prog)
 	fprintf(stdout, "         -o            alignment filename in SAM format [output.sam]\n");
 	fprintf(stdout, "         -bo           alignment filename in BAM format\n");
 	fprintf(stdout, "         -bz STR       with -bo: who compresses the BAM records, host (zlib) or device [host]\n");
+	fprintf(stdout, "         -fz STR       with bgzip-ped read files: who inflates them, host (zlib) or device [host]\n");
 	fprintf(stdout, "         -m            output multiple alignments\n");
 	fprintf(stdout, "         -g INT        max gaps (indels) [5]\n");
 	fprintf(stdout, "         -p            paired-end reads are interlaced in the same file\n");
@@ -69,6 +70,15 @@ int parse_cli(int argc, char **argv, Options &opt)
 				return -2;
 			}
 			opt.bz_device = v == "device";
+		}
+		else if (p == "-fz") {                           // (who inflates: the text, and so the alignments, are the same)
+			const std::string v = i + 1 < argc ? argv[++i] : "";
+			if (v != "host" && v != "device") {
+				fprintf(stdout, "Error! -fz expects host or device\n");
+				usage(argv[0]);
+				return -2;
+			}
+			opt.fz_device = v == "device";
 		}
 		else if (p == "-gpu" && i + 1 < argc) {          // one device, or a list a,b,c: one process per device, the input sharded
 			opt.devices.clear();
@@ -237,6 +247,8 @@ int cli_main(int argc, char **argv, KernelBackend *(*make_backend)(const Options
 		fprintf(stdout, "Alignment output: %s\n", opt.out_name.c_str());
 		if (getenv("KART_AMD_VERBOSE") && !launcher) fprintf(stdout, "mapping seconds (index load excluded): %.3f\n", st.map_seconds);
 		if (getenv("KART_AMD_VERBOSE")) fprintf(stdout, "chunks re-mapped after EstDistance speculation: %lld\n", (long long)st.respeculated);
+		if (getenv("KART_AMD_VERBOSE") && st.inflate_device_bytes + st.inflate_host_bytes > 0)
+			fprintf(stdout, "device inflate: %lld of %lld bytes of BGZF text (%.1f ms of kernels)\n", (long long)st.inflate_device_bytes, (long long)(st.inflate_device_bytes + st.inflate_host_bytes), st.inflate_device_ms);
 		if (getenv("KART_AMD_VERBOSE") && opt.bam) fprintf(stdout, "device deflate: %lld of %lld bytes\n", (long long)st.bgzf_device_bytes, (long long)(st.bgzf_device_bytes + st.bgzf_host_bytes));
 	}
 	return 0;

@@ -118,31 +118,53 @@ struct GzText {
 		gzbuffer(own, 1 << 20);
 		f = own;
 	}
+	// -fz device: the members are inflated by the device (mapper.hpp) instead of the zlib threads; gone again once a run() of it fails
+	std::unique_ptr<MemberInflater> inflater;
+	bool silent = false;
+	int64_t device_bytes = 0, host_bytes = 0;      // text of BGZF members the device / zlib inflated
+	double device_ms = 0;
+	void drop_inflater(const char *why)
+	{
+		if (!silent) fprintf(stderr, "Warning! %s: zlib inflates the rest of [%s]\n", why, path.c_str());
+		device_ms += inflater->device_ms();
+		inflater.reset();
+	}
 	void fill_bgzf(std::vector<char> &buf, size_t want)
 	{
 		const size_t at = buf.size();
-		// 1. the members that hold the next `want` bytes of text: one read of their span, then a walk over the headers
+		// 1. the members that hold the next `want` bytes of text: one read of their span (into the inflater's page-locked buffer where there is one),
+		// then a walk over the headers
 		std::vector<Member> mem;
 		size_t total = 0, span = 0;
 		bool foreign = false;
+		unsigned char *pk = nullptr;         // the span's bytes: pk[0, have)
+		size_t have = 0;
 		packed.clear();
+		auto room = [&](size_t bytes) {
+			if (inflater) {
+				if (unsigned char *p = inflater->src(bytes)) { pk = p; return; }
+				packed.assign(pk, pk + have);
+				drop_inflater("no page-locked memory for the members");
+			}
+			packed.resize(bytes);
+			pk = packed.data();
+		};
 		while (total < want && !eof && !foreign) {
 			const size_t guess = std::max<size_t>((size_t)1 << 20, (want - total) / 3);          // (FASTQ text packs ~3-5x)
-			const size_t have = packed.size();
-			packed.resize(have + guess);
-			ssize_t n = ::pread(fd, packed.data() + have, guess, pos + (off_t)have);
-			packed.resize(have + (n > 0 ? (size_t)n : 0));
+			room(have + guess);
+			ssize_t n = ::pread(fd, pk + have, guess, pos + (off_t)have);
+			have += n > 0 ? (size_t)n : 0;
 			const bool end_of_file = n <= 0 || (size_t)n < guess;
 			while (total < want) {
 				size_t csize = 0, hdr = 0;
-				const size_t left = packed.size() - span;
+				const size_t left = have - span;
 				if (left == 0) { if (end_of_file) eof = true; break; }
-				if (left < 18 || !member_shape(packed.data() + span, left, csize, hdr)) {
+				if (left < 18 || !member_shape(pk + span, left, csize, hdr)) {
 					if (left >= 18 || end_of_file) foreign = true;      // not a BGZF member (or a truncated one): gzread() decides what it is
 					break;
 				}
 				if (csize > left) { if (end_of_file) foreign = true; break; }
-				const unsigned char *t = packed.data() + span + csize - 4;
+				const unsigned char *t = pk + span + csize - 4;
 				Member m;
 				m.in = span; m.hdr = hdr; m.csize = csize;
 				m.isize = (size_t)t[0] | ((size_t)t[1] << 8) | ((size_t)t[2] << 16) | ((size_t)t[3] << 24);
@@ -153,44 +175,66 @@ struct GzText {
 			}
 			if (end_of_file) break;
 		}
-		// 2. inflate them side by side
+		// 2. inflate them: the device, else the zlib threads side by side
 		buf.resize(at + total);
-		std::atomic<size_t> next{0}, first_bad{mem.size()};
-		auto work = [&]() {
-			z_stream z;
-			memset(&z, 0, sizeof(z));
-			if (inflateInit2(&z, -15) != Z_OK) { first_bad.store(0); return; }
-			for (size_t k; (k = next.fetch_add(1)) < mem.size();) {
-				const Member &m = mem[k];
-				const unsigned char *in = packed.data() + m.in;
-				inflateReset(&z);
-				z.next_in = const_cast<unsigned char *>(in + m.hdr);
-				z.avail_in = (uInt)(m.csize - m.hdr - 8);
-				z.next_out = (unsigned char *)buf.data() + at + m.out;
-				z.avail_out = (uInt)m.isize;
-				int rc = inflate(&z, Z_FINISH);
-				const unsigned char *t = in + m.csize - 8;
-				const uLong want_crc = (uLong)t[0] | ((uLong)t[1] << 8) | ((uLong)t[2] << 16) | ((uLong)t[3] << 24);
-				bool good = rc == Z_STREAM_END && z.avail_out == 0 && z.avail_in == 0 &&
-				            crc32(crc32(0L, Z_NULL, 0), (const unsigned char *)buf.data() + at + m.out, (uInt)m.isize) == want_crc;
-				if (!good) { size_t cur = first_bad.load(); while (k < cur && !first_bad.compare_exchange_weak(cur, k)) {} }
+		size_t bad = mem.size();
+		bool on_device = false;
+		if (inflater && !mem.empty()) {
+			std::vector<int64_t> member_off(mem.size() + 1), text_off(mem.size() + 1);
+			for (size_t k = 0; k < mem.size(); ++k) { member_off[k] = (int64_t)mem[k].in; text_off[k] = (int64_t)mem[k].out; }
+			member_off[mem.size()] = (int64_t)span; text_off[mem.size()] = (int64_t)total;
+			const unsigned char *text = nullptr;
+			const int32_t *status = nullptr;
+			if (inflater->run(span, member_off.data(), text_off.data(), mem.size(), text, status)) {
+				on_device = true;
+				for (size_t k = 0; k < mem.size(); ++k)
+					if (status[k] != KG_INFLATE_OK) { bad = k; break; }
+				const size_t sound = bad < mem.size() ? mem[bad].out : total;
+				if (sound) memcpy(buf.data() + at, text, sound);
+				device_bytes += (int64_t)sound;
+			} else {
+				packed.assign(pk, pk + have);      // (the members lie in the inflater's buffer, which goes with it)
+				pk = packed.data();
+				drop_inflater("the device did not inflate a round of members");
 			}
-			inflateEnd(&z);
-		};
-		{
+		}
+		if (!on_device) {
+			std::atomic<size_t> next{0}, first_bad{mem.size()};
+			auto work = [&]() {
+				z_stream z;
+				memset(&z, 0, sizeof(z));
+				if (inflateInit2(&z, -15) != Z_OK) { first_bad.store(0); return; }
+				for (size_t k; (k = next.fetch_add(1)) < mem.size();) {
+					const Member &m = mem[k];
+					const unsigned char *in = pk + m.in;
+					inflateReset(&z);
+					z.next_in = const_cast<unsigned char *>(in + m.hdr);
+					z.avail_in = (uInt)(m.csize - m.hdr - 8);
+					z.next_out = (unsigned char *)buf.data() + at + m.out;
+					z.avail_out = (uInt)m.isize;
+					int rc = inflate(&z, Z_FINISH);
+					const unsigned char *t = in + m.csize - 8;
+					const uLong want_crc = (uLong)t[0] | ((uLong)t[1] << 8) | ((uLong)t[2] << 16) | ((uLong)t[3] << 24);
+					bool good = rc == Z_STREAM_END && z.avail_out == 0 && z.avail_in == 0 &&
+					            crc32(crc32(0L, Z_NULL, 0), (const unsigned char *)buf.data() + at + m.out, (uInt)m.isize) == want_crc;
+					if (!good) { size_t cur = first_bad.load(); while (k < cur && !first_bad.compare_exchange_weak(cur, k)) {} }
+				}
+				inflateEnd(&z);
+			};
 			const size_t nt = std::min<size_t>((size_t)threads, std::max<size_t>(1, mem.size() / 8));
 			std::vector<std::thread> th;
 			for (size_t t = 1; t < nt; ++t) th.emplace_back(work);
 			work();
 			for (std::thread &x : th) x.join();
+			bad = first_bad.load();
+			host_bytes += (int64_t)(bad < mem.size() ? mem[bad].out : total);
 		}
-		if (first_bad.load() < mem.size()) {
+		if (bad < mem.size()) {
 			// a damaged member: gzread() takes over AT it and delivers exactly what the reference's gzgets() loop would still see
 			// (the bytes before the damage, then the end of the library)
-			const size_t k = first_bad.load();
-			buf.resize(at + mem[k].out);
+			buf.resize(at + mem[bad].out);
 			close_bgzf();
-			replay(buf, delivered + mem[k].out);
+			replay(buf, delivered + mem[bad].out);
 			return;
 		}
 		pos += (off_t)span;
@@ -295,7 +339,7 @@ struct GzText {
 		}
 		std::vector<char> tmp;
 		fill(tmp, std::min(cap, (size_t)64 << 20));
-		memcpy(dst, tmp.data(), tmp.size());
+		if (!tmp.empty()) memcpy(dst, tmp.data(), tmp.size());
 		return tmp.size();
 	}
 	void fill(std::vector<char> &buf, size_t want)

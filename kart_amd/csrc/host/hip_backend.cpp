@@ -99,11 +99,41 @@ template <class T> struct PinnedBuf {
 	}
 };
 
+// kg_inflater_* behind GzText::fill_bgzf(): the buffers start at a round of FASTQ text (64 MB, packed ~4 : 1) and grow with what a round brings
+class HipInflater : public MemberInflater {
+public:
+	explicit HipInflater(kg_inflater *k) : k_(k) {}
+	~HipInflater() override { kg_inflater_destroy(k_); }
+	unsigned char *src(size_t bytes) override
+	{
+		if ((int64_t)bytes > src_cap_) {
+			if (kg_inflater_reserve(k_, (int64_t)bytes, 0, 0) != KG_OK) return nullptr;
+			src_cap_ = (int64_t)bytes;
+		}
+		return kg_inflater_src(k_);
+	}
+	bool run(size_t src_bytes, const int64_t *member_off, const int64_t *text_off, size_t n, const unsigned char *&text, const int32_t *&status) override
+	{
+		if (kg_inflater_reserve(k_, 0, text_off[n], (int64_t)n) != KG_OK) return false;
+		double ms = 0;
+		const uint8_t *t = nullptr;
+		if (kg_inflater_run(k_, (int64_t)src_bytes, member_off, text_off, (int64_t)n, &t, &status, &ms) != KG_OK) return false;
+		text = t;
+		ms_ += ms;
+		return true;
+	}
+	double device_ms() const override { return ms_; }
+private:
+	kg_inflater *k_;
+	int64_t src_cap_ = 0;
+	double ms_ = 0;
+};
+
 class HipBackend : public KernelBackend {
 public:
 	double t_frag_in = 0, t_frag_call = 0; int64_t n_frag_calls = 0;
 	double t_seed = 0, t_cands = 0, t_copy = 0, t_align = 0, t_reccopy = 0;   // KART_AMD_VERBOSE: where the per-batch device stage spends its time
-	HipBackend(kg_index *ix, const Options &opt) : ix_(ix), threads_(std::max(1, std::min(opt.threads, 16)))
+	HipBackend(kg_index *ix, const Options &opt) : ix_(ix), device_(opt.device), threads_(std::max(1, std::min(opt.threads, 16)))
 	{
 		kg_index_info(ix_, &info_);
 		int64_t max_reads = std::max<int64_t>(opt.batch_reads, 4000ll * 4 * std::max(1, opt.threads)) + 8192;
@@ -143,6 +173,12 @@ public:
 		}
 		stream_.reset(new HipStream(s, cfg));
 		return stream_.get();
+	}
+	std::unique_ptr<MemberInflater> inflater() override
+	{
+		kg_inflater *k = nullptr;
+		if (kg_inflater_create(device_, (int64_t)24 << 20, (int64_t)64 << 20, 4096, &k) != KG_OK) return nullptr;
+		return std::unique_ptr<MemberInflater>(new HipInflater(k));
 	}
 	int min_seed_len() const override { return info_.min_seed_len; }
 	void *host_alloc(size_t bytes) override { return kg_host_alloc(bytes); }
@@ -371,6 +407,7 @@ private:
 	int cur_ = 0;                   // the slot of the batch seeded last
 	bool long_used_ = false;
 	kg_index *ix_;
+	int device_;
 	int threads_;
 	std::mutex nw_mu_, frag_mu_;
 	static constexpr int kFragSets = 5;        // 3 calls in flight + the one whose results are being read + one spare

@@ -238,6 +238,7 @@ int run_mapping(const Options &opt, const RefData &ref, KernelBackend &kern, FIL
 			const int per_file = std::max(1, opt.threads / (sep ? 2 : 1));
 			if (!src.g1.try_bgzf(f1.c_str(), per_file)) src.g1.try_pgz(f1.c_str(), per_file);
 			if (sep && !src.g2.try_bgzf(opt.files2[lib].c_str(), per_file)) src.g2.try_pgz(opt.files2[lib].c_str(), per_file);
+			src.g1.silent = src.g2.silent = opt.silent;
 		}
 		if (shard.active()) {
 			// only a single library of plain 4-line FASTQ is split; anything else is mapped by shard 0 alone
@@ -253,9 +254,18 @@ int run_mapping(const Options &opt, const RefData &ref, KernelBackend &kern, FIL
 				continue;
 			}
 		}
+		// -fz device: a BGZF file's members go to the device, an inflater per mate file (a backend without one: zlib, as without the flag); made
+		// here, behind the shards that have nothing to map
+		for (GzText *g : {&src.g1, &src.g2})
+			if (opt.fz_device && g->fd >= 0) g->inflater = cx.kern.inflater();
 		double tl = now_s();
 		map_library(cx, src, out, stats, tot, shard, shard_out);
 		tot.t_lib += now_s() - tl;
+		src.p1.reset(); src.p2.reset();                   // (the files' writer threads have ended: their counters stand)
+		for (GzText *g : {&src.g1, &src.g2}) {
+			stats.inflate_device_bytes += g->device_bytes; stats.inflate_host_bytes += g->host_bytes;
+			stats.inflate_device_ms += g->device_ms + (g->inflater ? g->inflater->device_ms() : 0);
+		}
 	}
 	const bool last_writer = !shard.active() || (shard.solo ? shard.rank == 0 : shard.rank == shard.count - 1);
 	const size_t bam_eof_bytes = 28;                     // (an empty BGZF block)

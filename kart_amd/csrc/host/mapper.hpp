@@ -36,6 +36,7 @@ struct Options {
 	bool silent = false;      // -silent
 	bool bam = false;         // -bo: BAM instead of SAM (src/main.cpp:155-158)
 	bool bz_device = false;   // -bz device: the BGZF blocks of a -bo run that goes through the stream are compressed on the device (default: host, zlib)
+	bool fz_device = false;   // -fz device: the members of bgzip-ped read files are inflated on the device (default: host, zlib on the -t threads)
 	int device = 0;
 	std::vector<int> devices;       // -gpu a,b,c: one process per listed device, the input sharded between them
 	int shard_rank = 0, shard_count = 1;   // this process maps shard_rank of shard_count contiguous chunk ranges of the library ...
@@ -125,8 +126,22 @@ struct FragJobs {
 	void clear() { f1.clear(); o1.assign(1, 0); g.clear(); oo.clear(); gl.clear(); owner.clear(); ops = status = nullptr; len = nullptr; cols = 0; }
 };
 
+// BGZF members in, their text out (kg_inflater_*, include/kart_amd.h) for GzText::fill_bgzf(): a round's members are read straight into src(),
+// run() inflates them.  One per read file (the two mate files are filled side by side); its calls do not overlap.
+struct MemberInflater {
+	virtual ~MemberInflater() {}
+	// room for `bytes` of members (what an earlier, smaller call's buffer held is kept; that buffer is gone); null: no memory, the earlier buffer stays
+	virtual unsigned char *src(size_t bytes) = 0;
+	// member i is src[member_off[i], member_off[i + 1]) and becomes text[text_off[i], text_off[i + 1]) (KG_INFLATE_*: status[i]); text and status are the
+	// inflater's, valid until the next call.  false: the device did nothing (a HIP error, no memory)
+	virtual bool run(size_t src_bytes, const int64_t *member_off, const int64_t *text_off, size_t n, const unsigned char *&text, const int32_t *&status) = 0;
+	virtual double device_ms() const { return 0; }      // the launches so far, as HIP events timed them
+};
+
 struct KernelBackend {
 	virtual ~KernelBackend() {}
+	// -fz device: an inflater for one read file, or null: this backend has none (zlib inflates, as without the flag)
+	virtual std::unique_ptr<MemberInflater> inflater() { return nullptr; }
 	// GenerateNormalPairAlignment for the fragment pairs of several chunks in one call (fills ops / len / status of every part);
 	// false: this backend has no such stage -- the host plans every pair itself
 	virtual bool fragments_batch(std::vector<FragJobs *> &parts, bool pacbio, int max_gaps) { (void)parts; (void)pacbio; (void)max_gaps; return false; }
@@ -199,6 +214,8 @@ struct Stats {
 	int64_t rewritten_chunks = 0;   // (-parts, a later shard) chunks whose text was written a second time because settling changed a chunk in front of them
 	int64_t stream_reads = 0;   // reads that went through the device's FASTQ-in / SAM-out stream
 	int64_t bgzf_device_bytes = 0, bgzf_host_bytes = 0;   // -bo through the stream: file bytes of its chunks that the device compressed (-bz device) / the host's zlib did
+	int64_t inflate_device_bytes = 0, inflate_host_bytes = 0;   // text bytes of the BGZF members of read files that the device inflated (-fz device) / zlib did
+	double inflate_device_ms = 0;                               // ... and the device's time for them (HIP events around the launches)
 	kg_stream_timing_t device{};   // ... and what their batches cost on the device (HIP events on the lanes' streams, summed)
 	double lane_seconds[6] = {0, 0, 0, 0, 0, 0};   // ... and what the lanes' host threads waited for / worked on (kh_stats_t::lane_seconds), summed over `lanes` threads
 	int lanes = 0;
