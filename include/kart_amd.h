@@ -125,7 +125,8 @@ int  kg_device_count(void);                 /* number of usable HIP devices (0 i
 
 /* ---- index ------------------------------------------------------------------------------ */
 /* Reads <prefix>.bwt/.sa/.ann/.amb/.pac (BWA 0.7-era format written by the reference's
- * bwt_index) and uploads the FM-index + 2-bit reference to `device`. */
+ * bwt_index) and uploads the FM-index + 2-bit reference to `device`; the holes of
+ * .amb (offset, length and character of every run of an ambiguous base) go along for kg_stream_set_tags. */
 int  kg_index_load(const char *prefix, int device, int sa_mode, kg_index **out);
 void kg_index_destroy(kg_index *ix);
 int  kg_index_info(const kg_index *ix, kg_index_info_t *info);
@@ -407,6 +408,17 @@ int   kg_stream_set_format(kg_stream *s, int format);
 #define KG_STREAM_INPUT_FASTQ 0
 #define KG_STREAM_INPUT_FASTA 1
 int   kg_stream_set_input(kg_stream *s, int input);
+/* Which optional fields the records carry beyond the reference's NM / AS / XS: an OR of KG_STREAM_TAG_* (0, the default: none).  KG_STREAM_TAG_MD: every
+ * MAPPED record -- each chained record of a multi_hit read as well -- carries MD:Z behind XS ("\tMD:Z:<md>" in a SAM line, 'M' 'D' 'Z' <md> NUL in a BAM
+ * record); unmapped records and NM (the reference's rlen - score, no edit distance), AS, XS are unchanged.  <md> is the SAM specification's
+ * [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)*, a function of the record's SEQ as printed, its CIGAR, its contig and POS and the forward strand of the reference: an M
+ * column matches when the upper-cased read character is one of ACGT and equals the reference base, or the read character is '=' (samtools calmd's rule);
+ * any other column shows the reference base, D shows '^' and the deleted bases.  Inside a hole of .amb (an N or IUPAC run of the FASTA, random bases in
+ * .pac) the reference shows the hole's own character and matches nothing but '='; outside the record's contig it shows 'N' and the text is not read.
+ * Holds for every later kg_stream_map on all lanes; call it while no lane is inside a call (the lanes' output buffers grow to what the longer records
+ * need).  An unknown bit is KG_ERR_ARG. */
+#define KG_STREAM_TAG_MD 1
+int   kg_stream_set_tags(kg_stream *s, int tags);
 /* page-locked staging buffer of input file `file` (0 / 1) in lane `lane`, *capacity = max_window bytes */
 char *kg_stream_staging(kg_stream *s, int lane, int file, int64_t *capacity);
 /* staging[file][from, to) -> the lane's device window, asynchronously: a caller reads the next piece meanwhile */

@@ -29,6 +29,7 @@ KG_INPUT_ASCII = 0x100   # OR into mode: reads are given as characters, encoded 
 KG_SA_SAMPLED, KG_SA_FULL = 0, 1
 KG_STREAM_FORMAT_SAM, KG_STREAM_FORMAT_BAM, KG_STREAM_FORMAT_BAM_BGZF = 0, 1, 2   # kg_stream_set_format
 KG_STREAM_INPUT_FASTQ, KG_STREAM_INPUT_FASTA = 0, 1   # kg_stream_set_input
+KG_STREAM_TAG_MD = 1   # kg_stream_set_tags
 KG_SA_AUTO = -1                        # full below 2^32 text symbols; above: wide where the device has room, else compact (the host pipeline's default)
 KG_SA_FULL40 = 5                       # the compact index: 5-byte suffix-array entries, a quarter of the q-mer table, no triple planes
 KG_SA_FULL40_WIDE = 6                  # 5-byte suffix-array entries with the full q-mer table and the triple planes
@@ -55,7 +56,7 @@ ABI_SYMBOLS = (
     "kg_workspace_overflow", "kg_workspace_segment_fallbacks", "kg_workspace_set_profiling", "kg_workspace_set_single_steps", "kg_index_selfcheck", "kg_workspace_kernel_ms", "kg_seed_batch", "kg_candidates_batch", "kg_align_batch", "kg_align_reasons", "kg_seed_batch_device", "kg_nw_batch", "kg_nw_batch_device",
     "kg_fragments_batch", "kg_longread_batch", "kg_longread_reasons",
     "kg_stream_open", "kg_stream_close", "kg_stream_staging", "kg_stream_upload", "kg_stream_parse", "kg_stream_map", "kg_stream_fetch", "kg_stream_fetch_reads", "kg_stream_timing",
-    "kg_stream_group_absent", "kg_stream_group_abort", "kg_stream_set_format", "kg_stream_set_input",
+    "kg_stream_group_absent", "kg_stream_group_abort", "kg_stream_set_format", "kg_stream_set_input", "kg_stream_set_tags",
     "kg_bgzf_deflate", "kg_bgzf_inflate", "kg_inflater_create", "kg_inflater_reserve", "kg_inflater_src", "kg_inflater_run", "kg_inflater_destroy",
 )
 
@@ -226,6 +227,7 @@ def load_library() -> C.CDLL:
     L.kg_stream_group_abort.argtypes = [C.c_void_p]
     L.kg_stream_set_format.argtypes = [C.c_void_p, C.c_int]
     L.kg_stream_set_input.argtypes = [C.c_void_p, C.c_int]
+    L.kg_stream_set_tags.argtypes = [C.c_void_p, C.c_int]
     L.kg_stream_timing.argtypes = [C.c_void_p, C.POINTER(StreamTiming), C.c_int]
     L.kg_bgzf_deflate.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.kg_bgzf_inflate.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
@@ -651,6 +653,11 @@ class Stream:
         """what parse() takes the text for from here on: "fastq" (the default, four lines per record) or "fasta" (a header line, then sequence lines
         up to the next line that starts with '>'; the quality column of every record is "*")"""
         _check(self.lib.kg_stream_set_input(self.h, self.INPUTS.get(kind, -1) if isinstance(kind, str) else int(kind)), "kg_stream_set_input")
+
+    def set_tags(self, md: bool = False):
+        """which optional fields map() adds to the records from here on: md=True puts MD:Z (the mismatch / deletion string against the forward
+        reference, samtools calmd's rule) behind XS of every mapped record, in SAM lines and BAM records alike; the default is none"""
+        _check(self.lib.kg_stream_set_tags(self.h, KG_STREAM_TAG_MD if md else 0), "kg_stream_set_tags")
 
     def group_absent(self, lane: int, rounds: int):
         """seeding groups: lane `lane` has no batch for `rounds` rounds (< 0: until further notice, 0: it takes part again)"""

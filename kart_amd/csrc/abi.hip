@@ -231,6 +231,34 @@ int kg_index_load(const char *prefix, int device, int sa_mode, kg_index **out)
 				int q = (int)(30 * (1 - (float)(sc - sub) / sc) * log(sc) + 0.4999);
 				mq[(size_t)(kAlnMaxScore + 1) * 6 + (size_t)sc * (kAlnMaxScore + 1) + (size_t)nd] = (uint8_t)(q > 60 ? 60 : q < 0 ? 0 : q);
 			}
+		// .amb: "l_pac n_seqs n_holes" then per hole "offset len character" (bntseq.c:59-89)
+		{
+			struct HoleRec { int64_t start; int32_t len; uint8_t ch; };
+			std::vector<HoleRec> holes;
+			if (FILE *fa = fopen((pre + ".amb").c_str(), "r")) {
+				long long l = 0, off = 0;
+				int ns = 0, nh = 0, len = 0;
+				char ch[4];
+				if (fscanf(fa, "%lld%d%d", &l, &ns, &nh) == 3)
+					for (int i = 0; i < nh && fscanf(fa, "%lld%d%1s", &off, &len, ch) == 3; ++i)
+						if (off >= 0 && len > 0 && off + len <= ix->l_pac) holes.push_back(HoleRec{off, len, (uint8_t)toupper((unsigned char)ch[0])});
+				fclose(fa);
+			}
+			std::sort(holes.begin(), holes.end(), [](const HoleRec &a, const HoleRec &b) { return a.start < b.start; });
+			std::vector<int64_t> hs;
+			std::vector<int32_t> hl;
+			std::vector<uint8_t> hc;
+			for (const HoleRec &h : holes) { hs.push_back(h.start); hl.push_back(h.len); hc.push_back(h.ch); }
+			ix->n_holes = (int)holes.size();
+			HIP_TRY(hipMalloc((void **)&ix->d_hole_start, 8 * hs.size() + 8));
+			HIP_TRY(hipMalloc((void **)&ix->d_hole_len, 4 * hl.size() + 8));
+			HIP_TRY(hipMalloc((void **)&ix->d_hole_char, hc.size() + 8));
+			if (!holes.empty()) {
+				HIP_TRY(hipMemcpy(ix->d_hole_start, hs.data(), 8 * hs.size(), hipMemcpyHostToDevice));
+				HIP_TRY(hipMemcpy(ix->d_hole_len, hl.data(), 4 * hl.size(), hipMemcpyHostToDevice));
+				HIP_TRY(hipMemcpy(ix->d_hole_char, hc.data(), hc.size(), hipMemcpyHostToDevice));
+			}
+		}
 		HIP_TRY(hipMalloc((void **)&ix->d_mapq_tab, mq.size()));
 		HIP_TRY(hipMemcpy(ix->d_mapq_tab, mq.data(), mq.size(), hipMemcpyHostToDevice));
 	}
@@ -394,6 +422,9 @@ void kg_index_destroy(kg_index *ix)
 	if (ix->d_end_chr) (void)hipFree(ix->d_end_chr);
 	if (ix->d_chr_tab) (void)hipFree(ix->d_chr_tab);
 	if (ix->d_mapq_tab) (void)hipFree(ix->d_mapq_tab);
+	if (ix->d_hole_start) (void)hipFree(ix->d_hole_start);
+	if (ix->d_hole_len) (void)hipFree(ix->d_hole_len);
+	if (ix->d_hole_char) (void)hipFree(ix->d_hole_char);
 	delete ix;
 }
 

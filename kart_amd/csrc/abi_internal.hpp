@@ -72,6 +72,11 @@ struct kg_index {
 	int32_t *d_end_chr = nullptr;      // contig of every key
 	int64_t *d_chr_tab = nullptr;      // [3 * n_contigs]: FowardLocation, ReverseLocation, len
 	uint8_t *d_mapq_tab = nullptr;     // EvaluateMAPQ's libm branch, tabulated (kg_align_batch)
+	// .amb: the runs of ambiguous characters of the FASTA, ascending (kg_stream_set_tags: MD:Z shows them in the place of the text's random bases)
+	int n_holes = 0;
+	int64_t *d_hole_start = nullptr;   // [n_holes]
+	int32_t *d_hole_len = nullptr;     // [n_holes]
+	uint8_t *d_hole_char = nullptr;    // [n_holes] upper case
 	uint64_t device_bytes = 0;
 };
 

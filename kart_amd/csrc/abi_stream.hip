@@ -162,6 +162,7 @@ struct kg_stream {
 	int min_seed_len = 13;
 	int format = KG_STREAM_FORMAT_SAM;                 // what kg_stream_map makes of the records (kg_stream_set_format)
 	int input = KG_STREAM_INPUT_FASTQ;                 // what kg_stream_parse takes the text for (kg_stream_set_input)
+	int tags = 0;                                      // KG_STREAM_TAG_*: the optional fields beyond NM / AS / XS (kg_stream_set_tags)
 	bool fasta_sized = false;                          // the record tables hold line_capacity / 2 records (a FASTA record can be two lines) and the FASTA arrays exist
 	std::mutex mu;
 	kg_stream_timing_t total{};
@@ -446,7 +447,7 @@ int kg_stream_set_format(kg_stream *s, int format)
 		return fail(KG_ERR_ARG, "kg_stream_set_format: unknown format %d (KG_STREAM_FORMAT_SAM, KG_STREAM_FORMAT_BAM or KG_STREAM_FORMAT_BAM_BGZF)", format);
 	HIP_TRY(hipSetDevice(s->ix->device));
 	// the lanes' output buffers hold a batch in the larger of the two formats from the first BAM run on
-	const int64_t want = out_capacity(s->cfg, format);
+	const int64_t want = out_capacity(s->cfg, format) + ((s->tags & KG_STREAM_TAG_MD) ? 32 * s->cfg.max_reads : 0);
 	for (Lane &l : s->lanes) {
 		if (l.d_sam_capacity < want) {
 			HIP_TRY(hipStreamSynchronize(l.ws->stream));
@@ -464,6 +465,27 @@ int kg_stream_set_format(kg_stream *s, int format)
 		}
 	}
 	s->format = format;
+	return KG_OK;
+}
+
+int kg_stream_set_tags(kg_stream *s, int tags)
+{
+	if (!s) return fail(KG_ERR_ARG, "kg_stream_set_tags: null stream");
+	if (tags & ~KG_STREAM_TAG_MD) return fail(KG_ERR_ARG, "kg_stream_set_tags: unknown tags 0x%x (KG_STREAM_TAG_MD)", tags);
+	HIP_TRY(hipSetDevice(s->ix->device));
+	// MD:Z of an ordinary record is a number or a few ("\tMD:Z:150": 10 bytes); a batch whose records need more grows the buffers in kg_stream_map
+	const int64_t want = out_capacity(s->cfg, s->format) + ((tags & KG_STREAM_TAG_MD) ? 32 * s->cfg.max_reads : 0);
+	for (Lane &l : s->lanes) {
+		if (l.d_sam_capacity < want) {
+			HIP_TRY(hipStreamSynchronize(l.ws->stream));
+			HIP_TRY(grow_device(l.d_sam, l.d_sam_capacity, want, (size_t)want));
+		}
+		if (l.h_sam_capacity < want) {
+			HIP_TRY(hipStreamSynchronize(l.ws->stream));
+			HIP_TRY(grow_pinned(l.h_sam, l.h_sam_capacity, want, (size_t)want));
+		}
+	}
+	s->tags = tags;
 	return KG_OK;
 }
 
@@ -689,6 +711,8 @@ struct MapCall {
 	int64_t n_seeds = 0, totals[2] = {0, 0};           // candidates and their seeds
 	AlnArgs a;
 	SamArgs q;
+	MdRef mdref{};                                     // what MD:Z needs of the index
+	bool md = false;                                   // the batch's records carry MD:Z (the stream's tags when its text was sized)
 	bool checksum = false;
 	bool bgzf = false;                                 // the BGZF launch of the batch is on the lane's stream (KG_STREAM_FORMAT_BAM_BGZF)
 	int64_t sam_bytes = 0, n_host = 0, extra = 0;      // bytes of text, reads handed back, extra records of -m
@@ -758,7 +782,16 @@ static int map_size_text(kg_stream *s, Lane &l, MapCall &m)
 	q.chr_names = s->d_chr_names; q.chr_name_off = s->d_chr_name_off;
 	q.sam_len = l.d_sam_len; q.sam_off = l.d_sam_off; q.sam = l.d_sam; q.sam_capacity = l.d_sam_capacity;
 	q.host_list = l.d_host_list; q.ctl = l.d_sam_ctl;
-	HIP_TRY(launch_text_size(q, s->format != KG_STREAM_FORMAT_SAM, l.d_scan, l.scan_bytes, s->ix->n_cu, st));
+	{
+		const kg_index *ix = s->ix;
+		const int n_chr = (int)ix->contigs.size();
+		m.mdref.text = ix->d_text; m.mdref.genome_size = ix->l_pac;
+		m.mdref.chr_fwd_start = ix->d_chr_tab; m.mdref.chr_len = ix->d_chr_tab + 2 * n_chr;
+		m.mdref.n_chr = n_chr; m.mdref.n_holes = ix->n_holes;
+		m.mdref.hole_start = ix->d_hole_start; m.mdref.hole_len = ix->d_hole_len; m.mdref.hole_char = ix->d_hole_char;
+	}
+	m.md = (s->tags & KG_STREAM_TAG_MD) != 0;
+	HIP_TRY(launch_text_size(q, s->format != KG_STREAM_FORMAT_SAM, m.md ? &m.mdref : nullptr, l.d_scan, l.scan_bytes, s->ix->n_cu, st));
 	int64_t *word = l.h_meta + FQM_WORDS;
 	HIP_TRY(hipMemcpyAsync(&word[LW_TEXT_BYTES], l.d_sam_off + n, 8, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(&word[LW_HOST_READS], l.d_sam_ctl, 8, hipMemcpyDeviceToHost, st));
@@ -818,7 +851,7 @@ static int map_bgzf(kg_stream *s, Lane &l, MapCall &m)
 static int map_format(kg_stream *s, Lane &l, MapCall &m)
 {
 	hipStream_t st = l.ws->stream;
-	HIP_TRY(launch_text_format(m.q, s->format != KG_STREAM_FORMAT_SAM, s->ix->n_cu, st));
+	HIP_TRY(launch_text_format(m.q, s->format != KG_STREAM_FORMAT_SAM, m.md ? &m.mdref : nullptr, s->ix->n_cu, st));
 	// measurement aid (bench.py's gpu_pipeline leg): the text summed on the device, for runs that never copy it into file pages (read per call: a session switches it on and off)
 	m.checksum = getenv("KG_STREAM_CHECKSUM") != nullptr;
 	if (m.checksum) HIP_TRY(launch_sam_checksum(m.q, s->ix->n_cu, st));

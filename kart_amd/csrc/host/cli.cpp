@@ -32,6 +32,7 @@ static void usage(const char *prog)
 	fprintf(stdout, "         -bz STR       with -bo: who compresses the BAM records, host (zlib) or device [host]\n");
 	fprintf(stdout, "         -fz STR       with bgzip-ped read files: who inflates them, host (zlib) or device [host]\n");
 	fprintf(stdout, "         -m            output multiple alignments\n");
+	fprintf(stdout, "         -md           add MD:Z (mismatches and deletions against the reference) to every mapped record; NM stays read length - AS, not an edit distance\n");
 	fprintf(stdout, "         -g INT        max gaps (indels) [5]\n");
 	fprintf(stdout, "         -p            paired-end reads are interlaced in the same file\n");
 	fprintf(stdout, "         -pacbio       pacbio data\n");
@@ -99,6 +100,7 @@ int parse_cli(int argc, char **argv, Options &opt)
 		else if (p == "-silent") opt.silent = true;
 		else if (p == "-pacbio") opt.pacbio = true;
 		else if (p == "-m") opt.multi_hit = true;
+		else if (p == "-md") opt.md = true;              // (a flag, not an environment knob: it changes the file's content)
 		else if (p == "-pair" || p == "-p") opt.paired = true;
 		else if (p == "-v" || p == "--version") { fprintf(stdout, "kart v2.5.6\n\n"); return -1; }
 		else if (p == "-knobs") {          // the environment variables the product reads (host/knobs.inc): none is needed, none changes a result

@@ -143,12 +143,15 @@ bool bam_from_sam_line(const std::map<std::string_view, int> &ref_id, const char
 	}
 	if (qual == "*" || qual.size() != l_seq) raw.append(l_seq, (char)0xFF);
 	else for (uint32_t i = 0; i < l_seq; ++i) raw += (char)(qual[i] - 33);
-	// optional fields: TAG:i:value only (what this program prints)
+	// optional fields: TAG:i:value and TAG:Z:value (what this program prints)
 	while (at < len) {
 		const char *tab = (const char *)memchr(line + at, '\t', len - at);
 		size_t e = tab ? (size_t)(tab - line) : len;
 		if (e - at >= 6 && line[at + 2] == ':' && line[at + 3] == 'i' && line[at + 4] == ':')
 			bam_put_int_tag(raw, line + at, strtoll(std::string(line + at + 5, e - at - 5).c_str(), nullptr, 10));
+		else if (e - at >= 5 && line[at + 2] == ':' && line[at + 3] == 'Z' && line[at + 4] == ':') {
+			raw.append(line + at, 2); raw += 'Z'; raw.append(line + at + 5, e - at - 5); raw += '\0';
+		}
 		at = e + 1;
 	}
 	uint32_t block = (uint32_t)(raw.size() - start - 4);

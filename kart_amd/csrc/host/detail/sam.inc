@@ -3,6 +3,8 @@
 // ----------------------------------------------------------------------------------------------
 // SAM text (src/Mapping.cpp:177-315; record formats in SURVEY.md App. D)
 // ----------------------------------------------------------------------------------------------
+#include "md.inc"       // the MD:Z field (-md); a part of this fragment: whoever includes the printer has it
+
 inline void append_int(std::string &out, long long v)   // what "%d" / "%lld" print
 {
 	char buf[24];
@@ -60,7 +62,7 @@ void sam_mapped_fields(const Ctx &cx, const Read &rd, int flag, int chr_idx, lon
 {
 	const std::string &chr = cx.ref.contigs[(size_t)chr_idx].name;
 	size_t at = out.size();
-	out.resize(at + rd.name.size() + chr.size() + cigar.size() + rd.seq.size() + rd.qual.size() + 192);
+	out.resize(at + rd.name.size() + chr.size() + cigar.size() + rd.seq.size() + rd.qual.size() + 192 + (cx.opt.md ? md_room(cigar) : 0));
 	char *p = &out[at];
 	p = put(p, rd.name); *p++ = '\t';
 	p = put_int(p, flag); *p++ = '\t';
@@ -71,6 +73,7 @@ void sam_mapped_fields(const Ctx &cx, const Read &rd, int flag, int chr_idx, lon
 	if (has_mate) { p = put(p, "\t=\t", 3); p = put_int(p, mate_pos); *p++ = '\t'; p = put_int(p, tlen); *p++ = '\t'; }
 	else p = put(p, "\t*\t0\t0\t", 7);
 	size_t n = rd.seq.size();
+	const char *const shown = p;                 // SEQ as printed: what MD compares
 	if (!flip) p = put(p, rd.seq);
 	else {
 		revcomp_into(p, rd.seq.data(), n);      // GetComplementarySeq, src/tools.cpp:19-29
@@ -82,6 +85,7 @@ void sam_mapped_fields(const Ctx &cx, const Read &rd, int flag, int chr_idx, lon
 	p = put(p, "\tNM:i:", 6); p = put_int(p, rd.rlen - score);
 	p = put(p, "\tAS:i:", 6); p = put_int(p, score);
 	p = put(p, "\tXS:i:", 6); p = put_int(p, sub_score);
+	if (cx.opt.md) { p = put(p, "\tMD:Z:", 6); p = md_put(p, cx.ref, chr_idx, pos, cigar, shown, n); }
 	*p++ = '\n';
 	out.resize((size_t)(p - out.data()));
 }

@@ -74,6 +74,10 @@ public:
 	{
 		if (kg_stream_set_input(s_, fasta ? KG_STREAM_INPUT_FASTA : KG_STREAM_INPUT_FASTQ) != KG_OK) die("kg_stream_set_input");
 	}
+	void set_tags(bool md) override
+	{
+		if (kg_stream_set_tags(s_, md ? KG_STREAM_TAG_MD : 0) != KG_OK) die("kg_stream_set_tags");
+	}
 	kg_stream *handle() const { return s_; }
 
 private:

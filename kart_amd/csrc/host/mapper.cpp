@@ -98,6 +98,17 @@ bool RefData::load(const std::string &prefix, std::string &err, int threads)
 		contigs.push_back(c);
 	}
 	fclose(fp);
+	// .amb: "l_pac n_seqs n_holes" then per hole "offset len character" (bntseq.c:59-89)
+	if (FILE *fa = fopen((prefix + ".amb").c_str(), "r")) {
+		long long l = 0, off = 0;
+		int ns = 0, nh = 0, len = 0;
+		char ch[4];
+		if (fscanf(fa, "%lld%d%d", &l, &ns, &nh) == 3)
+			for (int i = 0; i < nh && fscanf(fa, "%lld%d%1s", &off, &len, ch) == 3; ++i)
+				if (off >= 0 && len > 0 && off + len <= genome_size) holes.push_back(Hole{off, len, (char)toupper((unsigned char)ch[0])});
+		fclose(fa);
+		std::sort(holes.begin(), holes.end(), [](const Hole &a, const Hole &b) { return a.start < b.start; });
+	}
 	std::vector<unsigned char> pac;
 	if (!slurp(prefix + ".pac", pac) || (int64_t)pac.size() < genome_size / 4 + 1) { err = "cannot read " + prefix + ".pac"; return false; }
 	// both strands as characters (src/bwt_index.cpp:242-258), one .pac byte = four bases at a time; the 2L bytes

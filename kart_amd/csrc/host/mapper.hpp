@@ -36,6 +36,7 @@ struct Options {
 	bool silent = false;      // -silent
 	bool bam = false;         // -bo: BAM instead of SAM (src/main.cpp:155-158)
 	bool bz_device = false;   // -bz device: the BGZF blocks of a -bo run that goes through the stream are compressed on the device (default: host, zlib)
+	bool md = false;          // -md: every mapped record carries MD:Z behind XS (the mismatch / deletion string against the forward reference; NM stays rlen - score)
 	bool fz_device = false;   // -fz device: the members of bgzip-ped read files are inflated on the device (default: host, zlib on the -t threads)
 	int device = 0;
 	std::vector<int> devices;       // -gpu a,b,c: one process per listed device, the input sharded between them
@@ -98,6 +99,8 @@ struct StreamBackend {
 	virtual void set_format(bool bam, bool bgzf = false) { (void)bam; (void)bgzf; }
 	// what parse() takes the text for from here on: 4-line FASTQ, or (fasta) FASTA records (kg_stream_set_input); while no lane works
 	virtual void set_input(bool fasta) { (void)fasta; }
+	// which optional fields the records carry beyond NM / AS / XS from here on (kg_stream_set_tags): md = MD:Z on every mapped record; while no lane works
+	virtual void set_tags(bool md) { (void)md; }
 };
 
 // The fragment pairs of one chunk whose alignment GenerateNormalPairAlignment (src/tools.cpp:142-223) is to produce -- 8-mer partition,
@@ -199,10 +202,17 @@ struct Contig {
 };
 
 // RestoreReferenceInfo (reference src/bwt_index.cpp:230-259): contigs, ChrLocMap, RefSequence
+// one line of .amb: a run of one ambiguous character of the FASTA (bntseq.c:125-141), where .pac holds random bases
+struct Hole {
+	int64_t start, len;      // forward-strand coordinate of its first base, bases
+	char ch;                 // the character, upper case
+};
+
 struct RefData {
 	int64_t genome_size = 0, two_genome_size = 0;
 	std::vector<Contig> contigs;
 	std::map<int64_t, int> chr_end;     // last coordinate of each strand copy -> contig index
+	std::vector<Hole> holes;            // .amb, ascending (-md shows a hole's own character, not the random base)
 	std::unique_ptr<char[], void (*)(void *)> seq{nullptr, free};   // 2L + 1, forward then reverse complement (2 MB-aligned, huge pages)
 	bool load(const std::string &prefix, std::string &err, int threads = 16);
 };

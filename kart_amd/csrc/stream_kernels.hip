@@ -24,6 +24,8 @@
 //                                       lanes move each read's pieces -- name, FLAG .. TLEN, sequence (reverse-complemented for a
 //                                       record shown on the other strand), qualities (reversed likewise), NM / AS / XS.
 //   bam_size_kernel / bam_format_kernel the same records as BAM (kg_stream_set_format): fixed-width fields, bases packed to 4 bits, qualities less 33
+//   (all four are templates on kMd: with kg_stream_set_tags(KG_STREAM_TAG_MD) every mapped record carries MD:Z behind XS, kernels/md_tag.inc; without, the
+//   instantiation is the code as it was before the tag existed)
 // Byte work, HBM-bound, no MFMA.  Everything is integer / character arithmetic; results are bit-identical to the host pipeline's
 // text (tests/test_stream_gpu.py, and every SAM parity test runs through this path).
 #include "stream_kernels.hpp"
@@ -543,8 +545,15 @@ __device__ __forceinline__ ReadText read_text(const SamArgs &a, int64_t r)
 #define SAM_UNMAPPED_MID "\t*\t0\t0\t*\t*\t0\t0\t"
 #define SAM_UNMAPPED_TAIL "\tAS:i:0\tXS:i:0\n"
 
-// the bytes of one record's line (src/Mapping.cpp:181-186 / 225-230 unmapped, :199-223 / 246-262 / 297-302 mapped)
-__device__ int record_size(const SamArgs &a, const ReadText &t, const kg_aln_record &rec)
+#include "kernels/md_tag.inc"
+
+// MD in a lane's LDS slot (the lane-per-read path of either format kernel): at most this many characters; a record with a longer one takes the
+// record-by-record path, which prints it straight into the output
+constexpr int kMdLds = 58;
+
+// the bytes of one record's line (src/Mapping.cpp:181-186 / 225-230 unmapped, :199-223 / 246-262 / 297-302 mapped); kMd: "\tMD:Z:" and the string
+template <bool kMd>
+__device__ int record_size(const SamArgs &a, const ReadText &t, const kg_aln_record &rec, const uint8_t *seq, const MdArg<kMd> &md)
 {
 	if (rec.kind == KG_ALN_UNMAPPED)
 		return t.name_len + 1 + int_chars(rec.flag) + (int)(sizeof(SAM_UNMAPPED_MID) - 1) + t.rlen + 1 + t.qlen + (int)(sizeof(SAM_UNMAPPED_TAIL) - 1);
@@ -553,12 +562,18 @@ __device__ int record_size(const SamArgs &a, const ReadText &t, const kg_aln_rec
 	n += rec.has_mate ? 3 + int_chars(rec.mate_pos) + 1 + int_chars(rec.tlen) + 1 : 7;
 	n += t.rlen + 1 + t.qlen;
 	n += 6 + int_chars(t.rlen - rec.score) + 6 + int_chars(rec.score) + 6 + int_chars(rec.sub_score) + 1;
+	if constexpr (kMd) {
+		MdCount c;
+		md_walk(md.r, rec, seq, t.rlen, c);
+		n += 6 + c.n;
+	}
 	return n;
 }
 
 }  // namespace
 
-__global__ __launch_bounds__(256) void sam_size_kernel(SamArgs a)
+template <bool kMd>
+__global__ __launch_bounds__(256) void sam_size_kernel(SamArgs a, MdArg<kMd> md)
 {
 	for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.n_reads; r += (int64_t)gridDim.x * blockDim.x) {
 		const kg_aln_record &first = a.records[r];
@@ -567,7 +582,7 @@ __global__ __launch_bounds__(256) void sam_size_kernel(SamArgs a)
 			a.host_list[atomicAdd(&a.ctl[0], 1ull)] = (int32_t)r;
 		} else {
 			const ReadText t = read_text(a, r);
-			for (int64_t at = r; at >= 0; at = a.records[at].next) n += record_size(a, t, a.records[at]);
+			for (int64_t at = r; at >= 0; at = a.records[at].next) n += record_size<kMd>(a, t, a.records[at], a.enc + a.read_off[r], md);
 		}
 		a.sam_len[r] = n;
 	}
@@ -584,6 +599,9 @@ __global__ __launch_bounds__(256) void sam_size_kernel(SamArgs a)
 namespace {
 
 constexpr int kFmtA = 16, kFmtB = 96, kFmtT = 64, kFmtSlot = kFmtA + kFmtB + kFmtT;     // bytes of a lane's strings (every string 16-byte aligned: they are read back 16 bytes at a time)
+// with MD:Z: the tags in front of it (three numbers of at most 11 characters: 52 with the line feed), "\tMD:Z:" and kMdLds characters
+constexpr int kFmtTMd = 128, kFmtSlotMd = kFmtA + kFmtB + kFmtTMd;
+static_assert(52 + 6 + kMdLds <= kFmtTMd && kFmtTMd % 16 == 0 && kFmtTMd < 256, "the tags with MD must fit the lane's slot and FmtDesc::nT");
 
 struct FmtDesc {                       // what phase 2 needs for one read
 	const uint8_t *name, *qual, *seq, *chr;
@@ -594,7 +612,11 @@ struct FmtDesc {                       // what phase 2 needs for one read
 };
 
 // the fields of one record as text: A = "\tFLAG[\t]", B = the middle, T = the tags
-__device__ __forceinline__ void print_fields(const ReadText &t, const kg_aln_record &rec, char *A, char *B, char *T, int &nA, int &nB, int &nT)
+// kMdMode 0: no MD:Z (the code as it was).  1: a mapped record's MD behind XS, in T -- md_over: it has more than kMdLds characters and T is not whole.
+// 2: T of a mapped record ends behind XS; the caller prints "\tMD:Z:", the string and the line feed itself (print_md_tail)
+template <int kMdMode>
+__device__ __forceinline__ void print_fields(const ReadText &t, const kg_aln_record &rec, char *A, char *B, char *T, int &nA, int &nB, int &nT, const MdRef *R = nullptr,
+                                             const uint8_t *seq = nullptr, bool *md_over = nullptr)
 {
 	const bool mapped = rec.kind == KG_ALN_MAPPED;
 	char *q = A;
@@ -614,9 +636,28 @@ __device__ __forceinline__ void print_fields(const ReadText &t, const kg_aln_rec
 		q = put_lit(q, "\tNM:i:", 6); q = put_int(q, t.rlen - rec.score);
 		q = put_lit(q, "\tAS:i:", 6); q = put_int(q, rec.score);
 		q = put_lit(q, "\tXS:i:", 6); q = put_int(q, rec.sub_score);
-		*q++ = '\n';
+		if constexpr (kMdMode == 1) {
+			q = put_lit(q, "\tMD:Z:", 6);
+			MdWrite w(q, kMdLds);
+			md_walk(*R, rec, seq, t.rlen, w);
+			*md_over = w.n > kMdLds;
+			q += w.n > kMdLds ? kMdLds : w.n;
+		}
+		if constexpr (kMdMode != 2) *q++ = '\n';
 	} else q = put_lit(q, SAM_UNMAPPED_TAIL, (int)(sizeof(SAM_UNMAPPED_TAIL) - 1));
 	nT = (int)(q - T);
+}
+
+// (one lane) "\tMD:Z:", the string and the line feed of a mapped record at p, of which `room` bytes belong to the read's lines; returns their true number --
+// where that exceeds the room nothing is written past it, and the caller's count of the line's bytes shows the disagreement
+__device__ __forceinline__ int print_md_tail(const MdRef &R, const kg_aln_record &rec, const uint8_t *seq, int rlen, uint8_t *p, int64_t room)
+{
+	const int cap = room > 0x7FFFFFFFll ? 0x7FFFFFFF : room < 0 ? 0 : (int)room;
+	if (cap >= 6) put_lit(reinterpret_cast<char *>(p), "\tMD:Z:", 6);
+	MdWrite w(reinterpret_cast<char *>(p) + 6, cap >= 6 ? cap - 6 : 0);
+	md_walk(R, rec, seq, rlen, w);
+	if (6 + w.n < cap) p[6 + w.n] = '\n';
+	return 6 + w.n + 1;
 }
 
 // all lanes: one line from its pieces; returns the end
@@ -648,11 +689,13 @@ __device__ __forceinline__ uint8_t *copy_line(uint8_t *__restrict__ p, int lane,
 
 }  // namespace
 
-__global__ __launch_bounds__(64) void sam_format_kernel(SamArgs a)
+template <bool kMd>
+__global__ __launch_bounds__(64) void sam_format_kernel(SamArgs a, MdArg<kMd> md)
 {
+	constexpr int kFmtSlot = kMd ? kFmtSlotMd : kg::kFmtSlot;
 	__shared__ __attribute__((aligned(16))) char str[64 * kFmtSlot];
 	__shared__ FmtDesc desc[64];
-	__shared__ int chain_len[3];
+	__shared__ int chain_len[kMd ? 4 : 3];      // [3]: the bytes print_md_tail made
 	__shared__ int chunk_pre[65];          // phase 2b: chunks of the lines before line i
 	const int lane = threadIdx.x;
 	const int64_t n_groups = (a.n_reads + 63) >> 6;
@@ -679,8 +722,14 @@ __global__ __launch_bounds__(64) void sam_format_kernel(SamArgs a)
 					int nA = 0, nB = 0, nT = 0;
 					// (reads beyond what the 16-bit fields and the output buffer hold take the record-by-record path, which checks)
 					const bool wide = t.rlen > 32000 || t.name_len > 32000 || o1 > a.sam_capacity;
-					const bool chained = rec.next >= 0 || wide || (kind != KG_ALN_UNMAPPED && kind != KG_ALN_MAPPED);
-					if (!chained) print_fields(t, rec, str + lane * kFmtSlot, str + lane * kFmtSlot + kFmtA, str + lane * kFmtSlot + kFmtA + kFmtB, nA, nB, nT);
+					bool chained = rec.next >= 0 || wide || (kind != KG_ALN_UNMAPPED && kind != KG_ALN_MAPPED);
+					if constexpr (kMd) {
+						// (an MD beyond the slot: the record-by-record path as well)
+						bool over = false;
+						if (!chained) print_fields<1>(t, rec, str + lane * kFmtSlot, str + lane * kFmtSlot + kFmtA, str + lane * kFmtSlot + kFmtA + kFmtB, nA, nB, nT, &md.r, d.seq, &over);
+						chained = chained || over;
+					} else
+					if (!chained) print_fields<0>(t, rec, str + lane * kFmtSlot, str + lane * kFmtSlot + kFmtA, str + lane * kFmtSlot + kFmtA + kFmtB, nA, nB, nT);
 					d.nA = (uint8_t)nA; d.nB = (uint8_t)nB; d.nT = (uint8_t)nT;
 					d.flags = (uint8_t)(1 | (flip ? 2 : 0) | (flip != t.held_reversed ? 4 : 0) | (chained ? 8 : 0));
 				}
@@ -767,7 +816,7 @@ __global__ __launch_bounds__(64) void sam_format_kernel(SamArgs a)
 				if (rec.kind != KG_ALN_UNMAPPED && rec.kind != KG_ALN_MAPPED) continue;
 				const bool mapped = rec.kind == KG_ALN_MAPPED;
 				__syncthreads();
-				if (lane == 0) print_fields(t, rec, S, S + kFmtA, S + kFmtA + kFmtB, chain_len[0], chain_len[1], chain_len[2]);
+				if (lane == 0) print_fields<kMd ? 2 : 0>(t, rec, S, S + kFmtA, S + kFmtA + kFmtB, chain_len[0], chain_len[1], chain_len[2]);
 				__syncthreads();
 				const uint8_t *cn = a.chr_names;
 				int nc = 0;
@@ -775,6 +824,14 @@ __global__ __launch_bounds__(64) void sam_format_kernel(SamArgs a)
 				const bool flip = mapped && rec.flip;
 				p = copy_line(p, lane, t.name, t.name_len, S, chain_len[0], cn, nc, S + kFmtA, chain_len[1], seq, t.rlen, flip, t.qual, t.qlen, flip != t.held_reversed,
 				              S + kFmtA + kFmtB, chain_len[2]);
+				if constexpr (kMd) {
+					if (mapped) {
+						if (lane == 0) chain_len[3] = print_md_tail(md.r, rec, seq, t.rlen, p, room - (int64_t)(p - a.sam));
+						__syncthreads();
+						p += chain_len[3];
+						if ((int64_t)(p - a.sam) > room) break;      // (the size kernel counted another string: the check below reports it, nothing more is written)
+					}
+				}
 			}
 			if (lane == 0 && (int64_t)(p - a.sam) != room) atomicAdd(&a.ctl[1], 1ull);
 			++i;
@@ -798,6 +855,9 @@ namespace {
 constexpr int kBamCore = 36;                                     // block_size + the 32 fixed bytes
 constexpr int kBamH = 48, kBamC = 96, kBamT = 32, kBamSlot = kBamH + kBamC + kBamT;     // a lane's core, CIGAR words (KG_ALN_CIGAR_MAX / 2 ops at most) and tags
 static_assert(KG_ALN_CIGAR_MAX / 2 * 4 <= kBamC, "the CIGAR words of a record must fit the lane's slot");
+// with MD:Z: the three integer tags (7 bytes each at most), 'M' 'D' 'Z', kMdLds characters and the NUL
+constexpr int kBamTMd = 96, kBamSlotMd = kBamH + kBamC + kBamTMd;
+static_assert(21 + 3 + kMdLds + 1 <= kBamTMd && kBamTMd % 16 == 0, "the tags with MD must fit the lane's slot");
 
 struct BamDesc {                       // what phase 2 needs for one read
 	const uint8_t *name, *qual, *seq;
@@ -845,12 +905,19 @@ __device__ __forceinline__ int bam_cigar_ops(const kg_aln_record &rec)
 	return ops > kBamC / 4 ? kBamC / 4 : ops;       // (a number in front of every operation: never more)
 }
 
-__device__ int bam_record_size(const ReadText &t, const kg_aln_record &rec, int lseq)
+template <bool kMd>
+__device__ int bam_record_size(const ReadText &t, const kg_aln_record &rec, int lseq, const uint8_t *seq, const MdArg<kMd> &md)
 {
 	if (rec.kind != KG_ALN_UNMAPPED && rec.kind != KG_ALN_MAPPED) return 0;
 	if (bam_qual_breaks(t)) return bam_block_bytes(t.name_len, lseq) + (rec.kind == KG_ALN_MAPPED ? 4 * bam_cigar_ops(rec) : 0);
 	if (rec.kind == KG_ALN_UNMAPPED) return bam_block_bytes(t.name_len, lseq) + 8;
-	return bam_block_bytes(t.name_len, lseq) + 4 * bam_cigar_ops(rec) + bam_tag_bytes(t.rlen - rec.score) + bam_tag_bytes(rec.score) + bam_tag_bytes(rec.sub_score);
+	int n = bam_block_bytes(t.name_len, lseq) + 4 * bam_cigar_ops(rec) + bam_tag_bytes(t.rlen - rec.score) + bam_tag_bytes(rec.score) + bam_tag_bytes(rec.sub_score);
+	if constexpr (kMd) {
+		MdCount c;
+		md_walk(md.r, rec, seq, t.rlen, c);
+		n += 3 + c.n + 1;
+	}
+	return n;
 }
 
 __device__ __forceinline__ int bam_reg2bin(int64_t beg, int64_t end)      // SAMv1 5.3
@@ -865,7 +932,11 @@ __device__ __forceinline__ int bam_reg2bin(int64_t beg, int64_t end)      // SAM
 }
 
 // one record's core (H: nine words), CIGAR words (C) and tags (T); nC / nT in bytes
-__device__ __forceinline__ void bam_build(const ReadText &t, const kg_aln_record &rec, int lseq, uint32_t *H, uint32_t *C, uint8_t *T, int &nC, int &nT)
+// kMdMode 0: no MD:Z (the code as it was).  1: a mapped record's MD behind XS, in T -- md_n > kMdLds: it has that many characters and T is not whole.
+// 2: T ends behind XS and block_size counts the 3 + md_n + 1 bytes of MD behind it, which the caller writes itself (bam_md_tail); md_n < 0: the record has none
+template <int kMdMode>
+__device__ __forceinline__ void bam_build(const ReadText &t, const kg_aln_record &rec, int lseq, uint32_t *H, uint32_t *C, uint8_t *T, int &nC, int &nT, const MdRef *R = nullptr,
+                                          const uint8_t *seq = nullptr, int *md_n = nullptr)
 {
 	const bool mapped = rec.kind == KG_ALN_MAPPED;
 	int ops = 0;
@@ -890,12 +961,31 @@ __device__ __forceinline__ void bam_build(const ReadText &t, const kg_aln_record
 		q = bam_put_tag(q, 'A', 'S', 0);
 		q = bam_put_tag(q, 'X', 'S', 0);
 	}
+	int md_tail = 0;                          // bytes of MD behind T
+	if constexpr (kMdMode != 0) {
+		*md_n = -1;
+		if (mapped && !bam_qual_breaks(t)) {
+			if constexpr (kMdMode == 1) {
+				q[0] = 'M'; q[1] = 'D'; q[2] = 'Z';
+				MdWrite w(reinterpret_cast<char *>(q) + 3, kMdLds);
+				md_walk(*R, rec, seq, t.rlen, w);
+				*md_n = w.n;
+				q += 3 + (w.n > kMdLds ? kMdLds : w.n);
+				*q++ = 0;
+			} else {
+				MdCount c;
+				md_walk(*R, rec, seq, t.rlen, c);
+				*md_n = c.n;
+				md_tail = 3 + c.n + 1;
+			}
+		}
+	}
 	nC = 4 * ops;
 	nT = bam_qual_breaks(t) ? 0 : (int)(q - T);
 	const int64_t pos = mapped ? rec.pos - 1 : -1;
 	const int bin = bam_reg2bin(pos, pos + (ref_len > 0 ? ref_len : 1));
 	const bool mate = mapped && rec.has_mate;
-	H[0] = (uint32_t)(bam_block_bytes(t.name_len, lseq) + nC + nT - 4);
+	H[0] = (uint32_t)(bam_block_bytes(t.name_len, lseq) + nC + nT + md_tail - 4);
 	H[1] = mapped ? (uint32_t)rec.chr : 0xFFFFFFFFu;
 	H[2] = (uint32_t)pos;
 	H[3] = (uint32_t)((t.name_len + 1) & 255) | (uint32_t)((mapped ? rec.mapq : 0) & 255) << 8 | (uint32_t)(bin & 0xFFFF) << 16;
@@ -976,9 +1066,21 @@ __device__ __forceinline__ uint8_t *bam_copy_record(uint8_t *__restrict__ p, int
 	return p + nT;
 }
 
+// (one lane) 'M' 'D' 'Z', the md_n characters and the NUL of a mapped record at p, of which `room` bytes belong to the read's records; nothing is written past
+// the room (the caller's count of the record's bytes shows a disagreement)
+__device__ __forceinline__ void bam_md_tail(const MdRef &R, const kg_aln_record &rec, const uint8_t *seq, int rlen, uint8_t *p, int64_t room, int md_n)
+{
+	if (room < 3 + (int64_t)md_n + 1) return;
+	p[0] = 'M'; p[1] = 'D'; p[2] = 'Z';
+	MdWrite w(reinterpret_cast<char *>(p) + 3, md_n);
+	md_walk(R, rec, seq, rlen, w);
+	p[3 + md_n] = 0;
+}
+
 }  // namespace
 
-__global__ __launch_bounds__(256) void bam_size_kernel(SamArgs a)
+template <bool kMd>
+__global__ __launch_bounds__(256) void bam_size_kernel(SamArgs a, MdArg<kMd> md)
 {
 	for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.n_reads; r += (int64_t)gridDim.x * blockDim.x) {
 		const kg_aln_record &first = a.records[r];
@@ -987,7 +1089,7 @@ __global__ __launch_bounds__(256) void bam_size_kernel(SamArgs a)
 			a.host_list[atomicAdd(&a.ctl[0], 1ull)] = (int32_t)r;
 		} else {
 			const ReadText t = read_text(a, r);
-			for (int64_t at = r; at >= 0; at = a.records[at].next) n += bam_record_size(t, a.records[at], bam_lseq(a, r, t.rlen, a.records[at]));
+			for (int64_t at = r; at >= 0; at = a.records[at].next) n += bam_record_size<kMd>(t, a.records[at], bam_lseq(a, r, t.rlen, a.records[at]), a.enc + a.read_off[r], md);
 		}
 		a.sam_len[r] = n;
 	}
@@ -1000,11 +1102,13 @@ __global__ __launch_bounds__(256) void bam_size_kernel(SamArgs a)
 //      as ONE list of 16-byte chunks, lane l taking chunks l, l + 64, ...: a chunk of packed bases is made of 32 bases (two loads), the
 //      reversed form reads them from the read's other end and complements them; a chunk of qualities is 16 of them less 33.
 // A read with further records chained behind it (-m), or beyond the 16-bit descriptor fields, takes the record-by-record path.
-__global__ __launch_bounds__(64) void bam_format_kernel(SamArgs a)
+template <bool kMd>
+__global__ __launch_bounds__(64) void bam_format_kernel(SamArgs a, MdArg<kMd> md)
 {
+	constexpr int kBamSlot = kMd ? kBamSlotMd : kg::kBamSlot;
 	__shared__ __attribute__((aligned(16))) uint8_t str[64 * kBamSlot];
 	__shared__ BamDesc desc[64];
-	__shared__ int chain_len[2];
+	__shared__ int chain_len[kMd ? 3 : 2];      // [2]: the characters of the record's MD, or -1
 	__shared__ int chunk_pre[65];
 	__shared__ int tab_seen[65];           // [64]: some line of the group; [i]: line i -- a tab among its qualities (the column ends there: 0xFF)
 	const int lane = threadIdx.x;
@@ -1031,9 +1135,15 @@ __global__ __launch_bounds__(64) void bam_format_kernel(SamArgs a)
 					const bool flip = kind == KG_ALN_MAPPED && rec.flip;
 					int nC = 0, nT = 0;
 					const bool wide = t.rlen > 32000 || t.name_len > 32000 || o1 > a.sam_capacity;
-					const bool chained = rec.next >= 0 || wide || (kind != KG_ALN_UNMAPPED && kind != KG_ALN_MAPPED);
+					bool chained = rec.next >= 0 || wide || (kind != KG_ALN_UNMAPPED && kind != KG_ALN_MAPPED);
 					uint8_t *S = str + lane * kBamSlot;
-					if (!chained) bam_build(t, rec, lseq, reinterpret_cast<uint32_t *>(S), reinterpret_cast<uint32_t *>(S + kBamH), S + kBamH + kBamC, nC, nT);
+					if constexpr (kMd) {
+						// (an MD beyond the slot: the record-by-record path as well)
+						int md_n = -1;
+						if (!chained) bam_build<1>(t, rec, lseq, reinterpret_cast<uint32_t *>(S), reinterpret_cast<uint32_t *>(S + kBamH), S + kBamH + kBamC, nC, nT, &md.r, d.seq, &md_n);
+						chained = chained || md_n > kMdLds;
+					} else
+					if (!chained) bam_build<0>(t, rec, lseq, reinterpret_cast<uint32_t *>(S), reinterpret_cast<uint32_t *>(S + kBamH), S + kBamH + kBamC, nC, nT);
 					d.nC = (uint8_t)nC; d.nT = (uint8_t)nT;
 					const bool qfill = t.qlen != lseq || (lseq == 1 && t.qual[0] == '*') || bam_qual_breaks(t);
 					d.flags = (uint8_t)(1 | (flip ? 2 : 0) | (flip != t.held_reversed ? 4 : 0) | (chained ? 8 : 0) | (qfill ? 16 : 0));
@@ -1152,10 +1262,20 @@ __global__ __launch_bounds__(64) void bam_format_kernel(SamArgs a)
 				if (rec.kind != KG_ALN_UNMAPPED && rec.kind != KG_ALN_MAPPED) continue;
 				const int lseq = bam_lseq(a, r, t.rlen, rec);
 				__syncthreads();
-				if (lane == 0) bam_build(t, rec, lseq, reinterpret_cast<uint32_t *>(S), reinterpret_cast<uint32_t *>(S + kBamH), S + kBamH + kBamC, chain_len[0], chain_len[1]);
+				if constexpr (kMd) {
+					if (lane == 0) bam_build<2>(t, rec, lseq, reinterpret_cast<uint32_t *>(S), reinterpret_cast<uint32_t *>(S + kBamH), S + kBamH + kBamC, chain_len[0], chain_len[1], &md.r, seq, &chain_len[2]);
+				} else
+				if (lane == 0) bam_build<0>(t, rec, lseq, reinterpret_cast<uint32_t *>(S), reinterpret_cast<uint32_t *>(S + kBamH), S + kBamH + kBamC, chain_len[0], chain_len[1]);
 				__syncthreads();
 				const bool flip = rec.kind == KG_ALN_MAPPED && rec.flip;
 				p = bam_copy_record(p, lane, S, t.name, t.name_len, S + kBamH, chain_len[0], seq, lseq, flip, t.qual, t.qlen, flip != t.held_reversed, S + kBamH + kBamC, chain_len[1]);
+				if constexpr (kMd) {
+					if (chain_len[2] >= 0) {
+						if (lane == 0) bam_md_tail(md.r, rec, seq, t.rlen, p, room - (int64_t)(p - a.sam), chain_len[2]);
+						p += 3 + chain_len[2] + 1;
+						if ((int64_t)(p - a.sam) > room) break;      // (the size kernel counted another string: the check below reports it, nothing more is written)
+					}
+				}
 			}
 			if (lane == 0 && (int64_t)(p - a.sam) != room) atomicAdd(&a.ctl[1], 1ull);
 		}
@@ -1305,12 +1425,15 @@ hipError_t launch_group_rebase(const int64_t *g_seed_off, int64_t n, int64_t fir
 }
 
 // the size of every read's text and their scan, then the text itself; bam: BAM records in the place of the SAM lines (they count into the same slots)
-hipError_t launch_text_size(const SamArgs &a, bool bam, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream)
+hipError_t launch_text_size(const SamArgs &a, bool bam, const MdRef *md, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream)
 {
 	kt_begin(KT_SAM_SIZE, stream);
 	hipLaunchKernelGGL(sam_reset_kernel, dim3(1), dim3(64), 0, stream, a);
-	if (bam) hipLaunchKernelGGL(bam_size_kernel, dim3(grid_of(a.n_reads, 256, n_cu * 16)), dim3(256), 0, stream, a);
-	else hipLaunchKernelGGL(sam_size_kernel, dim3(grid_of(a.n_reads, 256, n_cu * 16)), dim3(256), 0, stream, a);
+	const dim3 grid(grid_of(a.n_reads, 256, n_cu * 16));
+	if (bam && md) hipLaunchKernelGGL(bam_size_kernel<true>, grid, dim3(256), 0, stream, a, MdArg<true>{*md});
+	else if (bam) hipLaunchKernelGGL(bam_size_kernel<false>, grid, dim3(256), 0, stream, a, MdArg<false>{});
+	else if (md) hipLaunchKernelGGL(sam_size_kernel<true>, grid, dim3(256), 0, stream, a, MdArg<true>{*md});
+	else hipLaunchKernelGGL(sam_size_kernel<false>, grid, dim3(256), 0, stream, a, MdArg<false>{});
 	size_t tb = scan_temp_bytes;
 	Wide32Iter it(a.sam_len, Widen32());
 	hipError_t e = hipcub::DeviceScan::ExclusiveSum(scan_temp, tb, it, a.sam_off, (int)(a.n_reads + 1), stream);
@@ -1319,12 +1442,15 @@ hipError_t launch_text_size(const SamArgs &a, bool bam, void *scan_temp, size_t 
 	return hipGetLastError();
 }
 
-hipError_t launch_text_format(const SamArgs &a, bool bam, int n_cu, hipStream_t stream)
+hipError_t launch_text_format(const SamArgs &a, bool bam, const MdRef *md, int n_cu, hipStream_t stream)
 {
 	if (a.n_reads <= 0) return hipSuccess;
 	kt_begin(KT_SAM_FORMAT, stream);
-	if (bam) hipLaunchKernelGGL(bam_format_kernel, dim3(grid_of((a.n_reads + 63) / 64, 1, n_cu * 64)), dim3(64), 0, stream, a);
-	else hipLaunchKernelGGL(sam_format_kernel, dim3(grid_of((a.n_reads + 63) / 64, 1, n_cu * 64)), dim3(64), 0, stream, a);
+	const dim3 grid(grid_of((a.n_reads + 63) / 64, 1, n_cu * 64));
+	if (bam && md) hipLaunchKernelGGL(bam_format_kernel<true>, grid, dim3(64), 0, stream, a, MdArg<true>{*md});
+	else if (bam) hipLaunchKernelGGL(bam_format_kernel<false>, grid, dim3(64), 0, stream, a, MdArg<false>{});
+	else if (md) hipLaunchKernelGGL(sam_format_kernel<true>, grid, dim3(64), 0, stream, a, MdArg<true>{*md});
+	else hipLaunchKernelGGL(sam_format_kernel<false>, grid, dim3(64), 0, stream, a, MdArg<false>{});
 	kt_end(KT_SAM_FORMAT, stream);
 	return hipGetLastError();
 }

@@ -64,6 +64,23 @@ struct FqArgs {
 	int64_t n_reads;           // (materialise) reads of the batch, as the plan settled it
 };
 
+// what the MD:Z field needs of the index (kg_stream_set_tags; kernels/md_tag.inc): the 2-bit text, the contigs' places on its forward strand, and the holes of
+// .amb (runs of one ambiguous character in the FASTA, random bases in the text), ascending
+struct MdRef {
+	const uint8_t *text;
+	int64_t genome_size;             // bases of the forward strand
+	const int64_t *chr_fwd_start;    // [n_chr]
+	const int64_t *chr_len;          // [n_chr]
+	int32_t n_chr, n_holes;
+	const int64_t *hole_start;       // [n_holes] forward-strand coordinate of the hole's first base
+	const int32_t *hole_len;         // [n_holes]
+	const uint8_t *hole_char;        // [n_holes] the hole's character, upper case
+};
+
+// a kernel's last argument: the above where the kernel prints MD:Z, nothing where it does not (those kernels' arguments are what they were)
+template <bool kMd> struct MdArg {};
+template <> struct MdArg<true> { MdRef r; };
+
 // the SAM text of a batch
 struct SamArgs {
 	FqWindow w[2];
@@ -90,8 +107,9 @@ hipError_t launch_fq_parse(const FqArgs &a, void *scan_temp, size_t scan_temp_by
 hipError_t launch_fq_materialise(const FqArgs &a, int n_cu, hipStream_t stream);
 // the text of the batch: sizes and their scan, then the bytes; bam: BAM records in the place of the SAM lines (same arguments, same outputs:
 // sam_len / sam_off / sam hold the records' bytes)
-hipError_t launch_text_size(const SamArgs &a, bool bam, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream);
-hipError_t launch_text_format(const SamArgs &a, bool bam, int n_cu, hipStream_t stream);
+// md (may be null: none): every mapped record carries MD:Z behind XS
+hipError_t launch_text_size(const SamArgs &a, bool bam, const MdRef *md, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream);
+hipError_t launch_text_format(const SamArgs &a, bool bam, const MdRef *md, int n_cu, hipStream_t stream);
 hipError_t launch_sam_checksum(const SamArgs &a, int n_cu, hipStream_t stream);      // measurement aid: ctl[2] += byte sum, ctl[3] += line feeds of the text
 // grouped seeding: a lane's parsed batch published as a segment of its group's batch; the lane's seed offsets cut out of the group's
 hipError_t launch_group_publish(const int64_t *local_off, int64_t n, int64_t slots, int64_t enc_base, int64_t *g_off, int32_t *g_len, int n_cu, hipStream_t stream);
