@@ -419,6 +419,14 @@ int   kg_stream_set_input(kg_stream *s, int input);
  * need).  An unknown bit is KG_ERR_ARG. */
 #define KG_STREAM_TAG_MD 1
 int   kg_stream_set_tags(kg_stream *s, int tags);
+/* The read group of the records from here on: `id` (len bytes, 1 to 255, each in '!'..'~'; no NUL needed) makes EVERY record -- unmapped ones and each chained
+ * record of a multi_hit read as well -- carry RG:Z as its last optional field, behind XS and behind MD:Z where KG_STREAM_TAG_MD is set: "\tRG:Z:<id>" before a
+ * SAM line's line feed, 'R' 'G' 'Z' <id> NUL at the end of a BAM record (block_size counts it).  As everywhere, a BAM record is what the host's encoder makes of
+ * the SAM line: a record whose short quality line breaks the printed line has no tags and so no read group.  id == NULL (len 0) clears the read group (the
+ * default).  The @RG header line is the caller's to write.  An invalid id -- empty, longer than 255 bytes, a byte outside '!'..'~' -- is KG_ERR_ARG and leaves the
+ * earlier setting in place.  Holds for every later kg_stream_map on all lanes; call it while no lane is inside a call.  The call allocates nothing: a
+ * batch whose records with the field outgrow a lane's output buffers grows them in kg_stream_map, which knows the batch's size before it makes the text. */
+int   kg_stream_set_read_group(kg_stream *s, const char *id, int len);
 /* page-locked staging buffer of input file `file` (0 / 1) in lane `lane`, *capacity = max_window bytes */
 char *kg_stream_staging(kg_stream *s, int lane, int file, int64_t *capacity);
 /* staging[file][from, to) -> the lane's device window, asynchronously: a caller reads the next piece meanwhile */

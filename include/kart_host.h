@@ -76,7 +76,9 @@ int  kh_open(const char *index_prefix, int device, int threads, kh_session **out
 /* One mapping run.  argv holds the reference's command-line flags for the run (src/main.cpp:123-176): -f <files> [-f2
  * <files>] -o|-bo <out> [-m] [-p] [-pacbio] [-g INT] [-silent], plus this pipeline's -shard r/N -rendezvous FILE, -bz host|device (who compresses
  * a -bo run's blocks), -fz host|device (who inflates bgzip-ped read files: zlib on the session's threads, or the device; the output is the same)
- * and -md (MD:Z behind XS of every mapped record, which the reference does not print; every other byte of the output is unchanged);
+ * -md (MD:Z behind XS of every mapped record, which the reference does not print; every other byte of the output is unchanged)
+ * and -R '@RG\tID:..' (repeatable: once for all libraries or once per library of -f; "\t" or a real TAB; a header line per distinct -R behind the last @SQ
+ * and RG:Z:<ID> as the last field of every record, unmapped ones too; a line that is no read group line fails the call as a bad -bz value does);
  * -i, -t and -gpu are fixed by the session.  Returns 0 on success. */
 int  kh_map(kh_session *s, int argc, const char *const *argv, kh_stats_t *stats);
 /* (measurement aid: with KART_AMD_OUTPUT_NULL=1 in the environment of a kh_map call the text goes to /dev/null instead of the file named by

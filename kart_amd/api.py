@@ -56,7 +56,7 @@ ABI_SYMBOLS = (
     "kg_workspace_overflow", "kg_workspace_segment_fallbacks", "kg_workspace_set_profiling", "kg_workspace_set_single_steps", "kg_index_selfcheck", "kg_workspace_kernel_ms", "kg_seed_batch", "kg_candidates_batch", "kg_align_batch", "kg_align_reasons", "kg_seed_batch_device", "kg_nw_batch", "kg_nw_batch_device",
     "kg_fragments_batch", "kg_longread_batch", "kg_longread_reasons",
     "kg_stream_open", "kg_stream_close", "kg_stream_staging", "kg_stream_upload", "kg_stream_parse", "kg_stream_map", "kg_stream_fetch", "kg_stream_fetch_reads", "kg_stream_timing",
-    "kg_stream_group_absent", "kg_stream_group_abort", "kg_stream_set_format", "kg_stream_set_input", "kg_stream_set_tags",
+    "kg_stream_group_absent", "kg_stream_group_abort", "kg_stream_set_format", "kg_stream_set_input", "kg_stream_set_tags", "kg_stream_set_read_group",
     "kg_bgzf_deflate", "kg_bgzf_inflate", "kg_inflater_create", "kg_inflater_reserve", "kg_inflater_src", "kg_inflater_run", "kg_inflater_destroy",
 )
 
@@ -228,6 +228,7 @@ def load_library() -> C.CDLL:
     L.kg_stream_set_format.argtypes = [C.c_void_p, C.c_int]
     L.kg_stream_set_input.argtypes = [C.c_void_p, C.c_int]
     L.kg_stream_set_tags.argtypes = [C.c_void_p, C.c_int]
+    L.kg_stream_set_read_group.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     L.kg_stream_timing.argtypes = [C.c_void_p, C.POINTER(StreamTiming), C.c_int]
     L.kg_bgzf_deflate.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.kg_bgzf_inflate.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
@@ -658,6 +659,19 @@ class Stream:
         """which optional fields map() adds to the records from here on: md=True puts MD:Z (the mismatch / deletion string against the forward
         reference, samtools calmd's rule) behind XS of every mapped record, in SAM lines and BAM records alike; the default is none"""
         _check(self.lib.kg_stream_set_tags(self.h, KG_STREAM_TAG_MD if md else 0), "kg_stream_set_tags")
+
+    def set_read_group(self, id):
+        """the read group of the records map() makes from here on: `id` (str or bytes, 1 to 255 bytes in '!'..'~') puts RG:Z:<id> behind the last field
+        of EVERY record, unmapped ones too, in SAM lines and BAM records alike; None clears it (the default).  An id the library rejects raises
+        KartAmdError and the earlier one stays.  (The @RG header line is the caller's to write.)"""
+        if id is None:
+            _check(self.lib.kg_stream_set_read_group(self.h, None, 0), "kg_stream_set_read_group")
+            return
+        try:
+            raw = id.encode("ascii") if isinstance(id, str) else bytes(id)
+        except UnicodeEncodeError as e:
+            raise KartAmdError("kg_stream_set_read_group: the ID holds a character outside '!'..'~': %s" % e) from None
+        _check(self.lib.kg_stream_set_read_group(self.h, raw, len(raw)), "kg_stream_set_read_group")
 
     def group_absent(self, lane: int, rounds: int):
         """seeding groups: lane `lane` has no batch for `rounds` rounds (< 0: until further notice, 0: it takes part again)"""

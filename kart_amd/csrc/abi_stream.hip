@@ -163,6 +163,10 @@ struct kg_stream {
 	int format = KG_STREAM_FORMAT_SAM;                 // what kg_stream_map makes of the records (kg_stream_set_format)
 	int input = KG_STREAM_INPUT_FASTQ;                 // what kg_stream_parse takes the text for (kg_stream_set_input)
 	int tags = 0;                                      // KG_STREAM_TAG_*: the optional fields beyond NM / AS / XS (kg_stream_set_tags)
+	// the read group every record carries (kg_stream_set_read_group), in the two forms the kernels copy: "\tRG:Z:<ID>" at d_rg (6 + rg_len bytes) and
+	// 'R' 'G' 'Z' <ID> NUL at d_rg + kRgBamAt (4 + rg_len bytes); rg_len 0: none
+	uint8_t *d_rg = nullptr;
+	int rg_len = 0;
 	bool fasta_sized = false;                          // the record tables hold line_capacity / 2 records (a FASTA record can be two lines) and the FASTA arrays exist
 	std::mutex mu;
 	kg_stream_timing_t total{};
@@ -220,6 +224,17 @@ FqWindow window_of(const kg_stream *s, const Lane &l, int f)
 int64_t out_capacity(const kg_stream_config &cfg, int format)
 {
 	return 2 * cfg.max_window + (format != KG_STREAM_FORMAT_SAM ? 144 : 64) * cfg.max_reads + 4096;
+}
+
+// kg_stream::d_rg: the BAM form lies at this offset; behind either form there are 16 readable bytes (the kernels copy 16 bytes at a time)
+constexpr int kRgMaxId = 255, kRgBamAt = 512, kRgBytes = 1024;
+static_assert(6 + kRgMaxId + 16 <= kRgBamAt && kRgBamAt + 4 + kRgMaxId + 16 <= kRgBytes, "both forms of the longest ID and their slack must fit");
+
+// ... with the optional fields: MD:Z of an ordinary record is a number or a few ("\tMD:Z:150": 10 bytes); a batch whose records need more grows the
+// buffers in kg_stream_map.  The read group reserves nothing here: see kg_stream_set_read_group
+int64_t out_capacity(const kg_stream_config &cfg, int format, int tags)
+{
+	return out_capacity(cfg, format) + ((tags & KG_STREAM_TAG_MD) ? 32 : 0) * cfg.max_reads;
 }
 
 // A buffer that has to hold more: a new one of `bytes` in its place (nobody needs what the old one holds).  The caller synchronises the lane's
@@ -317,6 +332,8 @@ int kg_stream_open(kg_index *ix, const kg_stream_config *cfg, kg_stream **out)
 		HIP_TRY(hipMalloc((void **)&s->d_chr_name_off, 4 * off.size()));
 		HIP_TRY(hipMemcpy(s->d_chr_names, names.data(), names.size(), hipMemcpyHostToDevice));
 		HIP_TRY(hipMemcpy(s->d_chr_name_off, off.data(), 4 * off.size(), hipMemcpyHostToDevice));
+		HIP_TRY(hipMalloc((void **)&s->d_rg, kRgBytes));
+		HIP_TRY(hipMemset(s->d_rg, 0, kRgBytes));
 	}
 	s->lanes.resize((size_t)cfg->lanes);
 	const int64_t n = cfg->max_reads;
@@ -405,6 +422,7 @@ void kg_stream_close(kg_stream *s)
 	}
 	if (s->d_chr_names) (void)hipFree(s->d_chr_names);
 	if (s->d_chr_name_off) (void)hipFree(s->d_chr_name_off);
+	if (s->d_rg) (void)hipFree(s->d_rg);
 	delete s;
 }
 
@@ -440,14 +458,9 @@ static int bgzf_room(kg_stream *s, Lane &l, int64_t blocks, int64_t bytes)
 	return KG_OK;
 }
 
-int kg_stream_set_format(kg_stream *s, int format)
+// the lanes' output buffers, device and page-locked, hold `want` bytes (they only ever grow); nothing of a lane's is in flight afterwards
+static int grow_output(kg_stream *s, int64_t want)
 {
-	if (!s) return fail(KG_ERR_ARG, "kg_stream_set_format: null stream");
-	if (format != KG_STREAM_FORMAT_SAM && format != KG_STREAM_FORMAT_BAM && format != KG_STREAM_FORMAT_BAM_BGZF)
-		return fail(KG_ERR_ARG, "kg_stream_set_format: unknown format %d (KG_STREAM_FORMAT_SAM, KG_STREAM_FORMAT_BAM or KG_STREAM_FORMAT_BAM_BGZF)", format);
-	HIP_TRY(hipSetDevice(s->ix->device));
-	// the lanes' output buffers hold a batch in the larger of the two formats from the first BAM run on
-	const int64_t want = out_capacity(s->cfg, format) + ((s->tags & KG_STREAM_TAG_MD) ? 32 * s->cfg.max_reads : 0);
 	for (Lane &l : s->lanes) {
 		if (l.d_sam_capacity < want) {
 			HIP_TRY(hipStreamSynchronize(l.ws->stream));
@@ -457,6 +470,23 @@ int kg_stream_set_format(kg_stream *s, int format)
 			HIP_TRY(hipStreamSynchronize(l.ws->stream));
 			HIP_TRY(grow_pinned(l.h_sam, l.h_sam_capacity, want, (size_t)want));
 		}
+	}
+	return KG_OK;
+}
+
+int kg_stream_set_format(kg_stream *s, int format)
+{
+	if (!s) return fail(KG_ERR_ARG, "kg_stream_set_format: null stream");
+	if (format != KG_STREAM_FORMAT_SAM && format != KG_STREAM_FORMAT_BAM && format != KG_STREAM_FORMAT_BAM_BGZF)
+		return fail(KG_ERR_ARG, "kg_stream_set_format: unknown format %d (KG_STREAM_FORMAT_SAM, KG_STREAM_FORMAT_BAM or KG_STREAM_FORMAT_BAM_BGZF)", format);
+	HIP_TRY(hipSetDevice(s->ix->device));
+	// the lanes' output buffers hold a batch in the larger of the two formats from the first BAM run on
+	const int64_t want = out_capacity(s->cfg, format, s->tags);
+	{
+		int rc = grow_output(s, want);
+		if (rc != KG_OK) return rc;
+	}
+	for (Lane &l : s->lanes) {
 		if (format == KG_STREAM_FORMAT_BAM_BGZF) {
 			// (chunks of ReadChunkSize = 4000 reads and a read in a hundred handed back: a batch that cuts its records finer grows the tables)
 			HIP_TRY(hipStreamSynchronize(l.ws->stream));
@@ -473,19 +503,31 @@ int kg_stream_set_tags(kg_stream *s, int tags)
 	if (!s) return fail(KG_ERR_ARG, "kg_stream_set_tags: null stream");
 	if (tags & ~KG_STREAM_TAG_MD) return fail(KG_ERR_ARG, "kg_stream_set_tags: unknown tags 0x%x (KG_STREAM_TAG_MD)", tags);
 	HIP_TRY(hipSetDevice(s->ix->device));
-	// MD:Z of an ordinary record is a number or a few ("\tMD:Z:150": 10 bytes); a batch whose records need more grows the buffers in kg_stream_map
-	const int64_t want = out_capacity(s->cfg, s->format) + ((tags & KG_STREAM_TAG_MD) ? 32 * s->cfg.max_reads : 0);
-	for (Lane &l : s->lanes) {
-		if (l.d_sam_capacity < want) {
-			HIP_TRY(hipStreamSynchronize(l.ws->stream));
-			HIP_TRY(grow_device(l.d_sam, l.d_sam_capacity, want, (size_t)want));
-		}
-		if (l.h_sam_capacity < want) {
-			HIP_TRY(hipStreamSynchronize(l.ws->stream));
-			HIP_TRY(grow_pinned(l.h_sam, l.h_sam_capacity, want, (size_t)want));
-		}
-	}
+	int rc = grow_output(s, out_capacity(s->cfg, s->format, tags));
+	if (rc != KG_OK) return rc;
 	s->tags = tags;
+	return KG_OK;
+}
+
+int kg_stream_set_read_group(kg_stream *s, const char *id, int len)
+{
+	if (!s) return fail(KG_ERR_ARG, "kg_stream_set_read_group: null stream");
+	if (!id && len != 0) return fail(KG_ERR_ARG, "kg_stream_set_read_group: no ID but a length of %d", len);
+	if (id && (len < 1 || len > kRgMaxId)) return fail(KG_ERR_ARG, "kg_stream_set_read_group: an ID has 1 to %d bytes, not %d (NULL clears the read group)", kRgMaxId, len);
+	for (int i = 0; id && i < len; ++i)
+		if (id[i] < '!' || id[i] > '~') return fail(KG_ERR_ARG, "kg_stream_set_read_group: byte %d of the ID (0x%02x) is outside '!'..'~'", i, (unsigned)(unsigned char)id[i]);
+	HIP_TRY(hipSetDevice(s->ix->device));
+	if (id) {
+		// The lanes' output buffers stay as they are.  They are sized for the worst batch two full windows can hold, which an ordinary batch fills by half,
+		// and giving every lane a new device and page-locked buffer for 6 + len bytes more per read cost a run more than the field itself (0.8 s of a
+		// 1.5 s run).  kg_stream_map knows each batch's true size before its text is made and grows the buffers of a batch that needs it.
+		// no lane is inside a call, so no kernel reads the old forms: both new ones, each with zeros behind it
+		uint8_t form[kRgBytes] = {0};
+		memcpy(form, "\tRG:Z:", 6); memcpy(form + 6, id, (size_t)len);
+		memcpy(form + kRgBamAt, "RGZ", 3); memcpy(form + kRgBamAt + 3, id, (size_t)len);
+		HIP_TRY(hipMemcpy(s->d_rg, form, kRgBytes, hipMemcpyHostToDevice));
+	}
+	s->rg_len = id ? len : 0;
 	return KG_OK;
 }
 
@@ -782,6 +824,10 @@ static int map_size_text(kg_stream *s, Lane &l, MapCall &m)
 	q.chr_names = s->d_chr_names; q.chr_name_off = s->d_chr_name_off;
 	q.sam_len = l.d_sam_len; q.sam_off = l.d_sam_off; q.sam = l.d_sam; q.sam_capacity = l.d_sam_capacity;
 	q.host_list = l.d_host_list; q.ctl = l.d_sam_ctl;
+	// (the size kernel and the format kernel of a batch see the same read group: both take it from here)
+	const bool bam = s->format != KG_STREAM_FORMAT_SAM;
+	q.rg = s->rg_len > 0 ? s->d_rg + (bam ? kRgBamAt : 0) : nullptr;
+	q.rg_len = s->rg_len > 0 ? (bam ? 4 : 6) + s->rg_len : 0;
 	{
 		const kg_index *ix = s->ix;
 		const int n_chr = (int)ix->contigs.size();

@@ -33,12 +33,45 @@ static void usage(const char *prog)
 	fprintf(stdout, "         -fz STR       with bgzip-ped read files: who inflates them, host (zlib) or device [host]\n");
 	fprintf(stdout, "         -m            output multiple alignments\n");
 	fprintf(stdout, "         -md           add MD:Z (mismatches and deletions against the reference) to every mapped record; NM stays read length - AS, not an edit distance\n");
+	fprintf(stdout, "         -R STR        read group header line, e.g. '@RG\\tID:lane1\\tSM:sample'; every record gets RG:Z:<ID>. Once for all libraries, or once per library of -f\n");
 	fprintf(stdout, "         -g INT        max gaps (indels) [5]\n");
 	fprintf(stdout, "         -p            paired-end reads are interlaced in the same file\n");
 	fprintf(stdout, "         -pacbio       pacbio data\n");
 	fprintf(stdout, "         -gpu INT[,INT..] HIP device [0]; a list runs one process per device on contiguous parts of the input\n");
 	fprintf(stdout, "         -parts        with a device list: one output file per device, Output.0 Output.1 ... (their concatenation is the alignment file)\n");
 	fprintf(stdout, "         -v            version\n\n");
+}
+
+// the value of the ID: field of an @RG line (TAB-separated), empty where it has none
+static std::string read_group_id_of(const std::string &line)
+{
+	for (size_t at = line.find('\t'); at != std::string::npos; at = line.find('\t', at + 1))
+		if (line.compare(at + 1, 3, "ID:") == 0) {
+			const size_t end = line.find('\t', at + 1);
+			return line.substr(at + 4, end == std::string::npos ? std::string::npos : end - at - 4);
+		}
+	return std::string();
+}
+
+std::string Options::read_group_id(size_t lib) const
+{
+	if (read_groups.empty()) return std::string();
+	return read_group_id_of(read_groups.size() == 1 ? read_groups[0] : read_groups[std::min(lib, read_groups.size() - 1)]);
+}
+
+// what is wrong with a -R line, as the words behind "-R expects"; empty: nothing
+static std::string read_group_fault(const std::string &line)
+{
+	if (line.compare(0, 4, "@RG\t") != 0) return "a header line that begins with @RG and a TAB, as in '@RG\\tID:lane1\\tSM:sample'";
+	if (line.find('\n') != std::string::npos || line.find('\r') != std::string::npos) return "one header line: no line feed or carriage return";
+	bool has_id = false;
+	for (size_t at = line.find('\t'); at != std::string::npos; at = line.find('\t', at + 1)) has_id = has_id || line.compare(at + 1, 3, "ID:") == 0;
+	if (!has_id) return "an ID: field";
+	const std::string id = read_group_id_of(line);
+	if (id.empty() || id.size() > 255) return "an ID of 1 to 255 characters";
+	for (char ch : id)
+		if (ch < '!' || ch > '~') return "an ID of printable characters without blanks ('!' to '~')";
+	return std::string();
 }
 
 // returns 0 to proceed, otherwise -(exit code + 1)
@@ -101,6 +134,24 @@ int parse_cli(int argc, char **argv, Options &opt)
 		else if (p == "-pacbio") opt.pacbio = true;
 		else if (p == "-m") opt.multi_hit = true;
 		else if (p == "-md") opt.md = true;              // (a flag, not an environment knob: it changes the file's content)
+		else if (p == "-R") {                            // (bwa mem -R: a complete @RG line, "\t" for a TAB)
+			std::string line, why;
+			if (i + 1 < argc) {
+				for (const char *q = argv[++i]; *q; ++q) {
+					if (q[0] == '\\' && q[1] == 't') { line += '\t'; ++q; }
+					else line += *q;
+				}
+				why = read_group_fault(line);
+			} else why = "a header line behind it";
+			for (const std::string &g : opt.read_groups)
+				if (why.empty() && g != line && read_group_id_of(g) == read_group_id_of(line)) why = "one text per ID (" + read_group_id_of(line) + " is given with two)";
+			if (!why.empty()) {
+				fprintf(stdout, "Error! -R expects %s\n", why.c_str());
+				usage(argv[0]);
+				return -2;
+			}
+			opt.read_groups.push_back(line);
+		}
 		else if (p == "-pair" || p == "-p") opt.paired = true;
 		else if (p == "-v" || p == "--version") { fprintf(stdout, "kart v2.5.6\n\n"); return -1; }
 		else if (p == "-knobs") {          // the environment variables the product reads (host/knobs.inc): none is needed, none changes a result
@@ -116,6 +167,11 @@ int parse_cli(int argc, char **argv, Options &opt)
 	}
 	if (opt.files1.empty()) {
 		fprintf(stdout, "Error! Please specify a valid read input!\n");
+		usage(argv[0]);
+		return -2;
+	}
+	if (opt.read_groups.size() > 1 && opt.read_groups.size() != opt.files1.size()) {
+		fprintf(stdout, "Error! -R expects to be given once, or once per library (%zu of -f): it was given %zu times\n", opt.files1.size(), opt.read_groups.size());
 		usage(argv[0]);
 		return -2;
 	}

@@ -267,6 +267,7 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 		if (StreamBackend *sb = cx.kern.stream(full_reads + full_reads / 4 + chunk_limit, window, lanes, group)) {
 			sb->set_format(cx.opt.bam, cx.opt.bam && cx.opt.bz_device);      // (the stream is the session's: a -o run may follow a -bo run, a -bz host run a -bz device one)
 			sb->set_tags(cx.opt.md);                    // (... and a run with -md one without)
+			sb->set_read_group(cx.opt.read_group_id(cx.lib));      // (... and a library with a read group one without, or with another)
 			sb->set_input(!cx.fastq);                   // (... and a FASTQ library a FASTA one)
 			Options &o = const_cast<Options &>(cx.opt);
 			const int64_t keep = o.batch_reads;

@@ -24,7 +24,9 @@ void sam_unmapped(const Ctx &cx, const Read &rd, std::string &out)
 	out += "\t*\t0\t0\t*\t*\t0\t0\t";
 	out += rd.seq; out += '\t';
 	if (cx.fastq) append_qual(out, rd); else out += '*';
-	out += "\tAS:i:0\tXS:i:0\n";
+	out += "\tAS:i:0\tXS:i:0";
+	out += cx.rg_field;
+	out += '\n';
 }
 
 // raw-pointer writers for the record below: one capacity check per record instead of one per field
@@ -62,7 +64,7 @@ void sam_mapped_fields(const Ctx &cx, const Read &rd, int flag, int chr_idx, lon
 {
 	const std::string &chr = cx.ref.contigs[(size_t)chr_idx].name;
 	size_t at = out.size();
-	out.resize(at + rd.name.size() + chr.size() + cigar.size() + rd.seq.size() + rd.qual.size() + 192 + (cx.opt.md ? md_room(cigar) : 0));
+	out.resize(at + rd.name.size() + chr.size() + cigar.size() + rd.seq.size() + rd.qual.size() + 192 + (cx.opt.md ? md_room(cigar) : 0) + cx.rg_field.size());
 	char *p = &out[at];
 	p = put(p, rd.name); *p++ = '\t';
 	p = put_int(p, flag); *p++ = '\t';
@@ -86,6 +88,7 @@ void sam_mapped_fields(const Ctx &cx, const Read &rd, int flag, int chr_idx, lon
 	p = put(p, "\tAS:i:", 6); p = put_int(p, score);
 	p = put(p, "\tXS:i:", 6); p = put_int(p, sub_score);
 	if (cx.opt.md) { p = put(p, "\tMD:Z:", 6); p = md_put(p, cx.ref, chr_idx, pos, cigar, shown, n); }
+	p = put(p, cx.rg_field);                     // -R: the read group, the last field (empty without)
 	*p++ = '\n';
 	out.resize((size_t)(p - out.data()));
 }
@@ -104,7 +107,9 @@ void sam_one_record(const Ctx &cx, const Read &rd, const kg_aln_record &rec, std
 		out += "\t*\t0\t0\t*\t*\t0\t0\t";
 		out += rd.seq; out += '\t';
 		if (cx.fastq) append_qual(out, rd); else out += '*';
-		out += "\tAS:i:0\tXS:i:0\n";
+		out += "\tAS:i:0\tXS:i:0";
+		out += cx.rg_field;
+		out += '\n';
 	} else if (rec.kind == KG_ALN_MAPPED) {
 		std::string_view cigar(rec.cigar, rec.cigar_len);
 		if (rec.cigar_len == KG_ALN_CIGAR_POOLED) {             // a long read's CIGAR lies in the batch's text pool (kg_longread_batch)

@@ -173,6 +173,8 @@ struct Ctx {
 	bool fastq = true;
 	bool frag_service = false;     // -pacbio: GenerateNormalPairAlignment runs on the device in one call per batch (KernelBackend::fragments_batch)
 	std::map<std::string_view, int> bam_ref_id;   // -bo: contig name -> reference id
+	size_t lib = 0;                // the library being mapped: its place in Options::files1
+	std::string rg_field;          // -R: "\tRG:Z:<ID>" of the library being mapped, the last field of every record it prints; empty: none
 	const char *refseq() const { return ref.seq.get(); }
 };
 

@@ -78,6 +78,10 @@ public:
 	{
 		if (kg_stream_set_tags(s_, md ? KG_STREAM_TAG_MD : 0) != KG_OK) die("kg_stream_set_tags");
 	}
+	void set_read_group(const std::string &id) override
+	{
+		if (kg_stream_set_read_group(s_, id.empty() ? nullptr : id.data(), (int)id.size()) != KG_OK) die("kg_stream_set_read_group");
+	}
 	kg_stream *handle() const { return s_; }
 
 private:

@@ -207,6 +207,9 @@ int run_mapping(const Options &opt, const RefData &ref, KernelBackend &kern, FIL
 	if (shard.rank == 0) {
 		std::string header = "@PG\tID:kart\tPN:Kart\tVN:2.5.6\n";
 		for (size_t i = 0; i < ref.contigs.size(); ++i) header += "@SQ\tSN:" + ref.contigs[i].name + "\tLN:" + std::to_string((long long)ref.contigs[i].len) + "\n";
+		// -R: a line per distinct read group, in command-line order (parse_cli has rejected one ID with two texts)
+		for (size_t i = 0; i < opt.read_groups.size(); ++i)
+			if (std::find(opt.read_groups.begin(), opt.read_groups.begin() + (long)i, opt.read_groups[i]) == opt.read_groups.begin() + (long)i) header += opt.read_groups[i] + "\n";
 		if (opt.bam) {                                  // src/Mapping.cpp:676-680: the same text, as the BAM header
 			std::string blocks;
 			bgzf_append(bam_header(ref, header), blocks);
@@ -217,6 +220,8 @@ int run_mapping(const Options &opt, const RefData &ref, KernelBackend &kern, FIL
 		const std::string &f1 = opt.files1[lib];
 		bool gz = f1.size() >= 2 && f1.substr(f1.find_last_of('.') + 1) == "gz";   // src/Mapping.cpp:688
 		cx.fastq = is_fastq(f1);
+		cx.lib = lib;
+		cx.rg_field = opt.read_groups.empty() ? std::string() : "\tRG:Z:" + opt.read_group_id(lib);
 		Source src;
 		Input &in1 = src.in1, &in2 = src.in2;
 		bool want_fast = !gz && cx.fastq && !getenv("KART_AMD_NO_MMAP");

@@ -37,6 +37,10 @@ struct Options {
 	bool bam = false;         // -bo: BAM instead of SAM (src/main.cpp:155-158)
 	bool bz_device = false;   // -bz device: the BGZF blocks of a -bo run that goes through the stream are compressed on the device (default: host, zlib)
 	bool md = false;          // -md: every mapped record carries MD:Z behind XS (the mismatch / deletion string against the forward reference; NM stays rlen - score)
+	// -R (repeatable): complete @RG header lines as given, "\\t" made a TAB, no line feed; one for all libraries or one per library (files1), checked by
+	// parse_cli.  Every record of a library's reads carries RG:Z:<ID> of its line as its last field, and the header one line per distinct -R
+	std::vector<std::string> read_groups;
+	std::string read_group_id(size_t lib) const;    // the ID: value of library lib's line; empty without -R
 	bool fz_device = false;   // -fz device: the members of bgzip-ped read files are inflated on the device (default: host, zlib on the -t threads)
 	int device = 0;
 	std::vector<int> devices;       // -gpu a,b,c: one process per listed device, the input sharded between them
@@ -101,6 +105,8 @@ struct StreamBackend {
 	virtual void set_input(bool fasta) { (void)fasta; }
 	// which optional fields the records carry beyond NM / AS / XS from here on (kg_stream_set_tags): md = MD:Z on every mapped record; while no lane works
 	virtual void set_tags(bool md) { (void)md; }
+	// the read group every record carries as its last field from here on (kg_stream_set_read_group); empty: none; while no lane works
+	virtual void set_read_group(const std::string &id) { (void)id; }
 };
 
 // The fragment pairs of one chunk whose alignment GenerateNormalPairAlignment (src/tools.cpp:142-223) is to produce -- 8-mer partition,

@@ -25,7 +25,8 @@
 //                                       record shown on the other strand), qualities (reversed likewise), NM / AS / XS.
 //   bam_size_kernel / bam_format_kernel the same records as BAM (kg_stream_set_format): fixed-width fields, bases packed to 4 bits, qualities less 33
 //   (all four are templates on kMd: with kg_stream_set_tags(KG_STREAM_TAG_MD) every mapped record carries MD:Z behind XS, kernels/md_tag.inc; without, the
-//   instantiation is the code as it was before the tag existed)
+//   instantiation is the code as it was before the tag existed; and on kRg: with kg_stream_set_read_group EVERY record carries RG:Z as its last field,
+//   a constant of the batch copied from SamArgs::rg like a contig name -- the line feed of a SAM line then comes from the copy, not from the tags)
 // Byte work, HBM-bound, no MFMA.  Everything is integer / character arithmetic; results are bit-identical to the host pipeline's
 // text (tests/test_stream_gpu.py, and every SAM parity test runs through this path).
 #include "stream_kernels.hpp"
@@ -551,12 +552,20 @@ __device__ __forceinline__ ReadText read_text(const SamArgs &a, int64_t r)
 // record-by-record path, which prints it straight into the output
 constexpr int kMdLds = 58;
 
-// the bytes of one record's line (src/Mapping.cpp:181-186 / 225-230 unmapped, :199-223 / 246-262 / 297-302 mapped); kMd: "\tMD:Z:" and the string
-template <bool kMd>
+// the bytes of the read group field behind a record (SamArgs::rg), where the kernel writes one
+template <bool kRg> __device__ __forceinline__ int rg_bytes(const SamArgs &a)
+{
+	if constexpr (kRg) return a.rg_len;
+	else return 0;
+}
+
+// the bytes of one record's line (src/Mapping.cpp:181-186 / 225-230 unmapped, :199-223 / 246-262 / 297-302 mapped); kMd: "\tMD:Z:" and the string;
+// kRg: "\tRG:Z:<ID>" on either kind
+template <bool kMd, bool kRg>
 __device__ int record_size(const SamArgs &a, const ReadText &t, const kg_aln_record &rec, const uint8_t *seq, const MdArg<kMd> &md)
 {
 	if (rec.kind == KG_ALN_UNMAPPED)
-		return t.name_len + 1 + int_chars(rec.flag) + (int)(sizeof(SAM_UNMAPPED_MID) - 1) + t.rlen + 1 + t.qlen + (int)(sizeof(SAM_UNMAPPED_TAIL) - 1);
+		return t.name_len + 1 + int_chars(rec.flag) + (int)(sizeof(SAM_UNMAPPED_MID) - 1) + t.rlen + 1 + t.qlen + (int)(sizeof(SAM_UNMAPPED_TAIL) - 1) + rg_bytes<kRg>(a);
 	if (rec.kind != KG_ALN_MAPPED) return 0;
 	int n = t.name_len + 1 + int_chars(rec.flag) + 1 + (a.chr_name_off[rec.chr + 1] - a.chr_name_off[rec.chr]) + 1 + int_chars(rec.pos) + 1 + int_chars(rec.mapq) + 1 + rec.cigar_len;
 	n += rec.has_mate ? 3 + int_chars(rec.mate_pos) + 1 + int_chars(rec.tlen) + 1 : 7;
@@ -567,12 +576,12 @@ __device__ int record_size(const SamArgs &a, const ReadText &t, const kg_aln_rec
 		md_walk(md.r, rec, seq, t.rlen, c);
 		n += 6 + c.n;
 	}
-	return n;
+	return n + rg_bytes<kRg>(a);
 }
 
 }  // namespace
 
-template <bool kMd>
+template <bool kMd, bool kRg>
 __global__ __launch_bounds__(256) void sam_size_kernel(SamArgs a, MdArg<kMd> md)
 {
 	for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.n_reads; r += (int64_t)gridDim.x * blockDim.x) {
@@ -582,7 +591,7 @@ __global__ __launch_bounds__(256) void sam_size_kernel(SamArgs a, MdArg<kMd> md)
 			a.host_list[atomicAdd(&a.ctl[0], 1ull)] = (int32_t)r;
 		} else {
 			const ReadText t = read_text(a, r);
-			for (int64_t at = r; at >= 0; at = a.records[at].next) n += record_size<kMd>(a, t, a.records[at], a.enc + a.read_off[r], md);
+			for (int64_t at = r; at >= 0; at = a.records[at].next) n += record_size<kMd, kRg>(a, t, a.records[at], a.enc + a.read_off[r], md);
 		}
 		a.sam_len[r] = n;
 	}
@@ -614,7 +623,8 @@ struct FmtDesc {                       // what phase 2 needs for one read
 // the fields of one record as text: A = "\tFLAG[\t]", B = the middle, T = the tags
 // kMdMode 0: no MD:Z (the code as it was).  1: a mapped record's MD behind XS, in T -- md_over: it has more than kMdLds characters and T is not whole.
 // 2: T of a mapped record ends behind XS; the caller prints "\tMD:Z:", the string and the line feed itself (print_md_tail)
-template <int kMdMode>
+// kRg: T of either kind ends before the line feed: the caller puts the read group (SamArgs::rg) and the line feed behind the last field
+template <int kMdMode, bool kRg>
 __device__ __forceinline__ void print_fields(const ReadText &t, const kg_aln_record &rec, char *A, char *B, char *T, int &nA, int &nB, int &nT, const MdRef *R = nullptr,
                                              const uint8_t *seq = nullptr, bool *md_over = nullptr)
 {
@@ -643,21 +653,24 @@ __device__ __forceinline__ void print_fields(const ReadText &t, const kg_aln_rec
 			*md_over = w.n > kMdLds;
 			q += w.n > kMdLds ? kMdLds : w.n;
 		}
-		if constexpr (kMdMode != 2) *q++ = '\n';
-	} else q = put_lit(q, SAM_UNMAPPED_TAIL, (int)(sizeof(SAM_UNMAPPED_TAIL) - 1));
+		if constexpr (kMdMode != 2 && !kRg) *q++ = '\n';
+	} else q = put_lit(q, SAM_UNMAPPED_TAIL, (int)(sizeof(SAM_UNMAPPED_TAIL) - 1) - (kRg ? 1 : 0));
 	nT = (int)(q - T);
 }
 
-// (one lane) "\tMD:Z:", the string and the line feed of a mapped record at p, of which `room` bytes belong to the read's lines; returns their true number --
+// (one lane) "\tMD:Z:", the string and (kLf) the line feed of a mapped record at p, of which `room` bytes belong to the read's lines; returns their true number --
 // where that exceeds the room nothing is written past it, and the caller's count of the line's bytes shows the disagreement
+template <bool kLf>
 __device__ __forceinline__ int print_md_tail(const MdRef &R, const kg_aln_record &rec, const uint8_t *seq, int rlen, uint8_t *p, int64_t room)
 {
 	const int cap = room > 0x7FFFFFFFll ? 0x7FFFFFFF : room < 0 ? 0 : (int)room;
 	if (cap >= 6) put_lit(reinterpret_cast<char *>(p), "\tMD:Z:", 6);
 	MdWrite w(reinterpret_cast<char *>(p) + 6, cap >= 6 ? cap - 6 : 0);
 	md_walk(R, rec, seq, rlen, w);
-	if (6 + w.n < cap) p[6 + w.n] = '\n';
-	return 6 + w.n + 1;
+	if constexpr (kLf) {
+		if (6 + w.n < cap) p[6 + w.n] = '\n';
+	}
+	return 6 + w.n + (kLf ? 1 : 0);
 }
 
 // all lanes: one line from its pieces; returns the end
@@ -689,7 +702,7 @@ __device__ __forceinline__ uint8_t *copy_line(uint8_t *__restrict__ p, int lane,
 
 }  // namespace
 
-template <bool kMd>
+template <bool kMd, bool kRg>
 __global__ __launch_bounds__(64) void sam_format_kernel(SamArgs a, MdArg<kMd> md)
 {
 	constexpr int kFmtSlot = kMd ? kFmtSlotMd : kg::kFmtSlot;
@@ -726,10 +739,10 @@ __global__ __launch_bounds__(64) void sam_format_kernel(SamArgs a, MdArg<kMd> md
 					if constexpr (kMd) {
 						// (an MD beyond the slot: the record-by-record path as well)
 						bool over = false;
-						if (!chained) print_fields<1>(t, rec, str + lane * kFmtSlot, str + lane * kFmtSlot + kFmtA, str + lane * kFmtSlot + kFmtA + kFmtB, nA, nB, nT, &md.r, d.seq, &over);
+						if (!chained) print_fields<1, kRg>(t, rec, str + lane * kFmtSlot, str + lane * kFmtSlot + kFmtA, str + lane * kFmtSlot + kFmtA + kFmtB, nA, nB, nT, &md.r, d.seq, &over);
 						chained = chained || over;
 					} else
-					if (!chained) print_fields<0>(t, rec, str + lane * kFmtSlot, str + lane * kFmtSlot + kFmtA, str + lane * kFmtSlot + kFmtA + kFmtB, nA, nB, nT);
+					if (!chained) print_fields<0, kRg>(t, rec, str + lane * kFmtSlot, str + lane * kFmtSlot + kFmtA, str + lane * kFmtSlot + kFmtA + kFmtB, nA, nB, nT);
 					d.nA = (uint8_t)nA; d.nB = (uint8_t)nB; d.nT = (uint8_t)nT;
 					d.flags = (uint8_t)(1 | (flip ? 2 : 0) | (flip != t.held_reversed ? 4 : 0) | (chained ? 8 : 0));
 				}
@@ -753,6 +766,11 @@ __global__ __launch_bounds__(64) void sam_format_kernel(SamArgs a, MdArg<kMd> md
 				*p++ = '\t';
 				p += d.qlen;
 				p = lane_copy(p, end, S + kFmtA + kFmtB, d.nT);
+				if constexpr (kRg) {
+					// (every lane reads the same bytes of the stream's buffer: one fetch per instruction)
+					p = lane_copy(p, end, a.rg, a.rg_len);
+					*p++ = '\n';
+				}
 				if (p != end) atomicAdd(&a.ctl[1], 1ull);
 			}
 		}
@@ -816,7 +834,7 @@ __global__ __launch_bounds__(64) void sam_format_kernel(SamArgs a, MdArg<kMd> md
 				if (rec.kind != KG_ALN_UNMAPPED && rec.kind != KG_ALN_MAPPED) continue;
 				const bool mapped = rec.kind == KG_ALN_MAPPED;
 				__syncthreads();
-				if (lane == 0) print_fields<kMd ? 2 : 0>(t, rec, S, S + kFmtA, S + kFmtA + kFmtB, chain_len[0], chain_len[1], chain_len[2]);
+				if (lane == 0) print_fields<kMd ? 2 : 0, kRg>(t, rec, S, S + kFmtA, S + kFmtA + kFmtB, chain_len[0], chain_len[1], chain_len[2]);
 				__syncthreads();
 				const uint8_t *cn = a.chr_names;
 				int nc = 0;
@@ -826,11 +844,18 @@ __global__ __launch_bounds__(64) void sam_format_kernel(SamArgs a, MdArg<kMd> md
 				              S + kFmtA + kFmtB, chain_len[2]);
 				if constexpr (kMd) {
 					if (mapped) {
-						if (lane == 0) chain_len[3] = print_md_tail(md.r, rec, seq, t.rlen, p, room - (int64_t)(p - a.sam));
+						if (lane == 0) chain_len[3] = print_md_tail<!kRg>(md.r, rec, seq, t.rlen, p, room - (int64_t)(p - a.sam));
 						__syncthreads();
 						p += chain_len[3];
 						if ((int64_t)(p - a.sam) > room) break;      // (the size kernel counted another string: the check below reports it, nothing more is written)
 					}
+				}
+				if constexpr (kRg) {
+					// the read group and the line feed behind the record's last field, unmapped records too
+					if ((int64_t)(p - a.sam) + a.rg_len + 1 > room) { p += a.rg_len + 1; break; }      // (as above)
+					for (int k = lane; k < a.rg_len; k += 64) p[k] = a.rg[k];
+					if (lane == 0) p[a.rg_len] = '\n';
+					p += a.rg_len + 1;
 				}
 			}
 			if (lane == 0 && (int64_t)(p - a.sam) != room) atomicAdd(&a.ctl[1], 1ull);
@@ -905,19 +930,20 @@ __device__ __forceinline__ int bam_cigar_ops(const kg_aln_record &rec)
 	return ops > kBamC / 4 ? kBamC / 4 : ops;       // (a number in front of every operation: never more)
 }
 
+// rg: the bytes of the read group field ('R' 'G' 'Z' <ID> NUL) behind the tags of a record that has its tags, 0 = none
 template <bool kMd>
-__device__ int bam_record_size(const ReadText &t, const kg_aln_record &rec, int lseq, const uint8_t *seq, const MdArg<kMd> &md)
+__device__ int bam_record_size(const ReadText &t, const kg_aln_record &rec, int lseq, const uint8_t *seq, const MdArg<kMd> &md, int rg)
 {
 	if (rec.kind != KG_ALN_UNMAPPED && rec.kind != KG_ALN_MAPPED) return 0;
 	if (bam_qual_breaks(t)) return bam_block_bytes(t.name_len, lseq) + (rec.kind == KG_ALN_MAPPED ? 4 * bam_cigar_ops(rec) : 0);
-	if (rec.kind == KG_ALN_UNMAPPED) return bam_block_bytes(t.name_len, lseq) + 8;
+	if (rec.kind == KG_ALN_UNMAPPED) return bam_block_bytes(t.name_len, lseq) + 8 + rg;
 	int n = bam_block_bytes(t.name_len, lseq) + 4 * bam_cigar_ops(rec) + bam_tag_bytes(t.rlen - rec.score) + bam_tag_bytes(rec.score) + bam_tag_bytes(rec.sub_score);
 	if constexpr (kMd) {
 		MdCount c;
 		md_walk(md.r, rec, seq, t.rlen, c);
 		n += 3 + c.n + 1;
 	}
-	return n;
+	return n + rg;
 }
 
 __device__ __forceinline__ int bam_reg2bin(int64_t beg, int64_t end)      // SAMv1 5.3
@@ -934,8 +960,9 @@ __device__ __forceinline__ int bam_reg2bin(int64_t beg, int64_t end)      // SAM
 // one record's core (H: nine words), CIGAR words (C) and tags (T); nC / nT in bytes
 // kMdMode 0: no MD:Z (the code as it was).  1: a mapped record's MD behind XS, in T -- md_n > kMdLds: it has that many characters and T is not whole.
 // 2: T ends behind XS and block_size counts the 3 + md_n + 1 bytes of MD behind it, which the caller writes itself (bam_md_tail); md_n < 0: the record has none
+// rg: block_size counts that many bytes of a read group field behind the tags (and MD), which the caller copies there -- unless the record has no tags (nT == 0)
 template <int kMdMode>
-__device__ __forceinline__ void bam_build(const ReadText &t, const kg_aln_record &rec, int lseq, uint32_t *H, uint32_t *C, uint8_t *T, int &nC, int &nT, const MdRef *R = nullptr,
+__device__ __forceinline__ void bam_build(const ReadText &t, const kg_aln_record &rec, int lseq, uint32_t *H, uint32_t *C, uint8_t *T, int &nC, int &nT, int rg, const MdRef *R = nullptr,
                                           const uint8_t *seq = nullptr, int *md_n = nullptr)
 {
 	const bool mapped = rec.kind == KG_ALN_MAPPED;
@@ -985,7 +1012,7 @@ __device__ __forceinline__ void bam_build(const ReadText &t, const kg_aln_record
 	const int64_t pos = mapped ? rec.pos - 1 : -1;
 	const int bin = bam_reg2bin(pos, pos + (ref_len > 0 ? ref_len : 1));
 	const bool mate = mapped && rec.has_mate;
-	H[0] = (uint32_t)(bam_block_bytes(t.name_len, lseq) + nC + nT + md_tail - 4);
+	H[0] = (uint32_t)(bam_block_bytes(t.name_len, lseq) + nC + nT + md_tail + (nT ? rg : 0) - 4);
 	H[1] = mapped ? (uint32_t)rec.chr : 0xFFFFFFFFu;
 	H[2] = (uint32_t)pos;
 	H[3] = (uint32_t)((t.name_len + 1) & 255) | (uint32_t)((mapped ? rec.mapq : 0) & 255) << 8 | (uint32_t)(bin & 0xFFFF) << 16;
@@ -1079,7 +1106,7 @@ __device__ __forceinline__ void bam_md_tail(const MdRef &R, const kg_aln_record 
 
 }  // namespace
 
-template <bool kMd>
+template <bool kMd, bool kRg>
 __global__ __launch_bounds__(256) void bam_size_kernel(SamArgs a, MdArg<kMd> md)
 {
 	for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.n_reads; r += (int64_t)gridDim.x * blockDim.x) {
@@ -1089,7 +1116,7 @@ __global__ __launch_bounds__(256) void bam_size_kernel(SamArgs a, MdArg<kMd> md)
 			a.host_list[atomicAdd(&a.ctl[0], 1ull)] = (int32_t)r;
 		} else {
 			const ReadText t = read_text(a, r);
-			for (int64_t at = r; at >= 0; at = a.records[at].next) n += bam_record_size<kMd>(t, a.records[at], bam_lseq(a, r, t.rlen, a.records[at]), a.enc + a.read_off[r], md);
+			for (int64_t at = r; at >= 0; at = a.records[at].next) n += bam_record_size<kMd>(t, a.records[at], bam_lseq(a, r, t.rlen, a.records[at]), a.enc + a.read_off[r], md, rg_bytes<kRg>(a));
 		}
 		a.sam_len[r] = n;
 	}
@@ -1102,7 +1129,7 @@ __global__ __launch_bounds__(256) void bam_size_kernel(SamArgs a, MdArg<kMd> md)
 //      as ONE list of 16-byte chunks, lane l taking chunks l, l + 64, ...: a chunk of packed bases is made of 32 bases (two loads), the
 //      reversed form reads them from the read's other end and complements them; a chunk of qualities is 16 of them less 33.
 // A read with further records chained behind it (-m), or beyond the 16-bit descriptor fields, takes the record-by-record path.
-template <bool kMd>
+template <bool kMd, bool kRg>
 __global__ __launch_bounds__(64) void bam_format_kernel(SamArgs a, MdArg<kMd> md)
 {
 	constexpr int kBamSlot = kMd ? kBamSlotMd : kg::kBamSlot;
@@ -1140,10 +1167,10 @@ __global__ __launch_bounds__(64) void bam_format_kernel(SamArgs a, MdArg<kMd> md
 					if constexpr (kMd) {
 						// (an MD beyond the slot: the record-by-record path as well)
 						int md_n = -1;
-						if (!chained) bam_build<1>(t, rec, lseq, reinterpret_cast<uint32_t *>(S), reinterpret_cast<uint32_t *>(S + kBamH), S + kBamH + kBamC, nC, nT, &md.r, d.seq, &md_n);
+						if (!chained) bam_build<1>(t, rec, lseq, reinterpret_cast<uint32_t *>(S), reinterpret_cast<uint32_t *>(S + kBamH), S + kBamH + kBamC, nC, nT, rg_bytes<kRg>(a), &md.r, d.seq, &md_n);
 						chained = chained || md_n > kMdLds;
 					} else
-					if (!chained) bam_build<0>(t, rec, lseq, reinterpret_cast<uint32_t *>(S), reinterpret_cast<uint32_t *>(S + kBamH), S + kBamH + kBamC, nC, nT);
+					if (!chained) bam_build<0>(t, rec, lseq, reinterpret_cast<uint32_t *>(S), reinterpret_cast<uint32_t *>(S + kBamH), S + kBamH + kBamC, nC, nT, rg_bytes<kRg>(a));
 					d.nC = (uint8_t)nC; d.nT = (uint8_t)nT;
 					const bool qfill = t.qlen != lseq || (lseq == 1 && t.qual[0] == '*') || bam_qual_breaks(t);
 					d.flags = (uint8_t)(1 | (flip ? 2 : 0) | (flip != t.held_reversed ? 4 : 0) | (chained ? 8 : 0) | (qfill ? 16 : 0));
@@ -1166,6 +1193,10 @@ __global__ __launch_bounds__(64) void bam_format_kernel(SamArgs a, MdArg<kMd> md
 				p = lane_copy(p, bases, S + kBamH, d.nC);
 				p += ((d.lseq + 1) >> 1) + d.lseq;
 				p = lane_copy(p, end, S + kBamH + kBamC, d.nT);
+				if constexpr (kRg) {
+					// (a record without tags -- its quality line broke the printed line -- has no read group either)
+					if (d.nT) p = lane_copy(p, end, a.rg, a.rg_len);
+				}
 				if (p != end) atomicAdd(&a.ctl[1], 1ull);
 			}
 		}
@@ -1263,9 +1294,9 @@ __global__ __launch_bounds__(64) void bam_format_kernel(SamArgs a, MdArg<kMd> md
 				const int lseq = bam_lseq(a, r, t.rlen, rec);
 				__syncthreads();
 				if constexpr (kMd) {
-					if (lane == 0) bam_build<2>(t, rec, lseq, reinterpret_cast<uint32_t *>(S), reinterpret_cast<uint32_t *>(S + kBamH), S + kBamH + kBamC, chain_len[0], chain_len[1], &md.r, seq, &chain_len[2]);
+					if (lane == 0) bam_build<2>(t, rec, lseq, reinterpret_cast<uint32_t *>(S), reinterpret_cast<uint32_t *>(S + kBamH), S + kBamH + kBamC, chain_len[0], chain_len[1], rg_bytes<kRg>(a), &md.r, seq, &chain_len[2]);
 				} else
-				if (lane == 0) bam_build<0>(t, rec, lseq, reinterpret_cast<uint32_t *>(S), reinterpret_cast<uint32_t *>(S + kBamH), S + kBamH + kBamC, chain_len[0], chain_len[1]);
+				if (lane == 0) bam_build<0>(t, rec, lseq, reinterpret_cast<uint32_t *>(S), reinterpret_cast<uint32_t *>(S + kBamH), S + kBamH + kBamC, chain_len[0], chain_len[1], rg_bytes<kRg>(a));
 				__syncthreads();
 				const bool flip = rec.kind == KG_ALN_MAPPED && rec.flip;
 				p = bam_copy_record(p, lane, S, t.name, t.name_len, S + kBamH, chain_len[0], seq, lseq, flip, t.qual, t.qlen, flip != t.held_reversed, S + kBamH + kBamC, chain_len[1]);
@@ -1274,6 +1305,14 @@ __global__ __launch_bounds__(64) void bam_format_kernel(SamArgs a, MdArg<kMd> md
 						if (lane == 0) bam_md_tail(md.r, rec, seq, t.rlen, p, room - (int64_t)(p - a.sam), chain_len[2]);
 						p += 3 + chain_len[2] + 1;
 						if ((int64_t)(p - a.sam) > room) break;      // (the size kernel counted another string: the check below reports it, nothing more is written)
+					}
+				}
+				if constexpr (kRg) {
+					// the read group behind the record's tags (a record without tags has none)
+					if (chain_len[1] > 0) {
+						if ((int64_t)(p - a.sam) + a.rg_len > room) { p += a.rg_len; break; }      // (as above)
+						for (int k = lane; k < a.rg_len; k += 64) p[k] = a.rg[k];
+						p += a.rg_len;
 					}
 				}
 			}
@@ -1424,16 +1463,30 @@ hipError_t launch_group_rebase(const int64_t *g_seed_off, int64_t n, int64_t fir
 	return hipGetLastError();
 }
 
+// one of the four instantiations of a kernel pair: format and MD:Z at run time, the read group (kRg) as the caller found it
+template <bool kRg> static void launch_size(const SamArgs &a, bool bam, const MdRef *md, dim3 grid, hipStream_t stream)
+{
+	if (bam && md) hipLaunchKernelGGL((bam_size_kernel<true, kRg>), grid, dim3(256), 0, stream, a, MdArg<true>{*md});
+	else if (bam) hipLaunchKernelGGL((bam_size_kernel<false, kRg>), grid, dim3(256), 0, stream, a, MdArg<false>{});
+	else if (md) hipLaunchKernelGGL((sam_size_kernel<true, kRg>), grid, dim3(256), 0, stream, a, MdArg<true>{*md});
+	else hipLaunchKernelGGL((sam_size_kernel<false, kRg>), grid, dim3(256), 0, stream, a, MdArg<false>{});
+}
+template <bool kRg> static void launch_format(const SamArgs &a, bool bam, const MdRef *md, dim3 grid, hipStream_t stream)
+{
+	if (bam && md) hipLaunchKernelGGL((bam_format_kernel<true, kRg>), grid, dim3(64), 0, stream, a, MdArg<true>{*md});
+	else if (bam) hipLaunchKernelGGL((bam_format_kernel<false, kRg>), grid, dim3(64), 0, stream, a, MdArg<false>{});
+	else if (md) hipLaunchKernelGGL((sam_format_kernel<true, kRg>), grid, dim3(64), 0, stream, a, MdArg<true>{*md});
+	else hipLaunchKernelGGL((sam_format_kernel<false, kRg>), grid, dim3(64), 0, stream, a, MdArg<false>{});
+}
+
 // the size of every read's text and their scan, then the text itself; bam: BAM records in the place of the SAM lines (they count into the same slots)
 hipError_t launch_text_size(const SamArgs &a, bool bam, const MdRef *md, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream)
 {
 	kt_begin(KT_SAM_SIZE, stream);
 	hipLaunchKernelGGL(sam_reset_kernel, dim3(1), dim3(64), 0, stream, a);
 	const dim3 grid(grid_of(a.n_reads, 256, n_cu * 16));
-	if (bam && md) hipLaunchKernelGGL(bam_size_kernel<true>, grid, dim3(256), 0, stream, a, MdArg<true>{*md});
-	else if (bam) hipLaunchKernelGGL(bam_size_kernel<false>, grid, dim3(256), 0, stream, a, MdArg<false>{});
-	else if (md) hipLaunchKernelGGL(sam_size_kernel<true>, grid, dim3(256), 0, stream, a, MdArg<true>{*md});
-	else hipLaunchKernelGGL(sam_size_kernel<false>, grid, dim3(256), 0, stream, a, MdArg<false>{});
+	if (a.rg_len > 0) launch_size<true>(a, bam, md, grid, stream);
+	else launch_size<false>(a, bam, md, grid, stream);
 	size_t tb = scan_temp_bytes;
 	Wide32Iter it(a.sam_len, Widen32());
 	hipError_t e = hipcub::DeviceScan::ExclusiveSum(scan_temp, tb, it, a.sam_off, (int)(a.n_reads + 1), stream);
@@ -1447,10 +1500,8 @@ hipError_t launch_text_format(const SamArgs &a, bool bam, const MdRef *md, int n
 	if (a.n_reads <= 0) return hipSuccess;
 	kt_begin(KT_SAM_FORMAT, stream);
 	const dim3 grid(grid_of((a.n_reads + 63) / 64, 1, n_cu * 64));
-	if (bam && md) hipLaunchKernelGGL(bam_format_kernel<true>, grid, dim3(64), 0, stream, a, MdArg<true>{*md});
-	else if (bam) hipLaunchKernelGGL(bam_format_kernel<false>, grid, dim3(64), 0, stream, a, MdArg<false>{});
-	else if (md) hipLaunchKernelGGL(sam_format_kernel<true>, grid, dim3(64), 0, stream, a, MdArg<true>{*md});
-	else hipLaunchKernelGGL(sam_format_kernel<false>, grid, dim3(64), 0, stream, a, MdArg<false>{});
+	if (a.rg_len > 0) launch_format<true>(a, bam, md, grid, stream);
+	else launch_format<false>(a, bam, md, grid, stream);
 	kt_end(KT_SAM_FORMAT, stream);
 	return hipGetLastError();
 }

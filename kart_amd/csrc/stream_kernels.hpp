@@ -98,6 +98,10 @@ struct SamArgs {
 	int64_t sam_capacity;
 	int32_t *host_list;              // reads handed back (KG_ALN_HOST), in no particular order
 	unsigned long long *ctl;         // [0] entries of host_list, [1] format errors (a record whose text is not the size announced), [2] / [3] sam_checksum_kernel's sums
+	// the read group of the batch (kg_stream_set_read_group), in the form the launch's format copies behind every record's last field: "\tRG:Z:<ID>" for SAM
+	// lines, 'R' 'G' 'Z' <ID> NUL for BAM records; 16 readable bytes lie behind it (lane_copy).  rg_len: its bytes, 0 = none (the kRg = false kernels read neither)
+	const uint8_t *rg;
+	int32_t rg_len;
 };
 
 size_t fq_scan_temp_bytes(int64_t max_items);
@@ -107,7 +111,7 @@ hipError_t launch_fq_parse(const FqArgs &a, void *scan_temp, size_t scan_temp_by
 hipError_t launch_fq_materialise(const FqArgs &a, int n_cu, hipStream_t stream);
 // the text of the batch: sizes and their scan, then the bytes; bam: BAM records in the place of the SAM lines (same arguments, same outputs:
 // sam_len / sam_off / sam hold the records' bytes)
-// md (may be null: none): every mapped record carries MD:Z behind XS
+// md (may be null: none): every mapped record carries MD:Z behind XS; a.rg_len > 0: every record, unmapped ones too, carries RG:Z as its last field
 hipError_t launch_text_size(const SamArgs &a, bool bam, const MdRef *md, void *scan_temp, size_t scan_temp_bytes, int n_cu, hipStream_t stream);
 hipError_t launch_text_format(const SamArgs &a, bool bam, const MdRef *md, int n_cu, hipStream_t stream);
 hipError_t launch_sam_checksum(const SamArgs &a, int n_cu, hipStream_t stream);      // measurement aid: ctl[2] += byte sum, ctl[3] += line feeds of the text
