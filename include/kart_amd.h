@@ -218,8 +218,10 @@ int  kg_candidates_batch(kg_workspace *ws, int pacbio, int max_gaps, int64_t n_r
  *   CheckPairedFinalAlignments, Set{Paired,Single}AlignmentFlag, EvaluateMAPQ (src/Mapping.cpp:49-175, 429-480),
  *   and what OutputPairedAlignments / OutputSingledAlignments would print for every read (:177-315), with or without -m.
  * One record per read (with multi_hit further records of a read are chained through `next`; a record whose FLAG the reference
- * never assigns -- SURVEY App. B-12 -- carries unset_flag).  A read pair the device path does not take -- RescueUnpairedAlignment is due, a gap fragment needs the
- * 8-mer partition (both sides > 30), a candidate has more seeds or a longer CIGAR than the kernels hold -- comes back with
+ * never assigns -- SURVEY App. B-12 -- carries unset_flag).  A gap fragment with both sides > 30 is partitioned at its common 8-mers on the device
+ * (sides of 31 x 31 included).  A read pair the device path does not take -- RescueUnpairedAlignment is due, a gap fragment with a
+ * side above 255 bases or whose partition holds a read character other than A/C/G/T or more exact matches than the kernel keeps, a candidate with more
+ * than 12 seeds, more than 8 gap pairs between them or a CIGAR text above KG_ALN_CIGAR_MAX - 1 characters -- comes back with
  * kind KG_ALN_HOST on both reads: the caller maps it with its own implementation of the same reference code (the candidates
  * kg_candidates_batch returned are unmodified). */
 #define KG_ALN_NONE      0   /* nothing is printed for this read (the reference's loop finds no candidate to print) */
@@ -291,7 +293,8 @@ int  kg_longread_reasons(kg_workspace *ws, uint64_t out[16]);
 /* Running tallies (since the workspace was created) of why read pairs came back as KG_ALN_HOST: [0] candidate product too large,
  * [1] a mate-2 rescue window would be scanned, [2] rescue window too long, [3] mate not plain A/C/G/T or too long for the rescue
  * kernel, [4] too many exact-match runs in a window, [5] rescued candidate with too many pairs, [6] candidate with too many
- * seeds, [7] too many gap pairs, [8] a gap fragment needs the 8-mer partition (both sides > 30), [9] a device list was full,
+ * seeds, [7] too many gap pairs, [8] a gap fragment with a side above 255 bases, or whose 8-mer partition (both sides > 30) is outside what the
+ * partition kernel holds, [9] a device list was full,
  * [10] CIGAR too long, [11] score beyond the MAPQ table, [12] read too long.  Diagnostics only. */
 int  kg_align_reasons(kg_workspace *ws, uint64_t out[16]);
 

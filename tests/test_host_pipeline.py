@@ -31,6 +31,10 @@ CASES = {
     "edge_multi_lib": ["-f", "edge_1.fq", "edge_2.fq"],          # two single-end libraries
     # configs[0]: the read files of the reference's own test (run_test.sh:25-27; oracle/make_golden_reftest.py) on the small index
     "ref_test": ["-f", "ref_test_r1.fq", "-f2", "ref_test_r2.fq"],
+    # the indel-shape fixture (oracle/make_golden_shapes.py): constructed edits on the tile edges and decision thresholds of the candidate report
+    "shape_se": ["-f", "shape_1.fq.gz"],
+    "shape_pe": ["-f", "shape_1.fq.gz", "-f2", "shape_2.fq.gz"],
+    "shape_se_g20": ["-f", "shape_1.fq.gz", "-g", "20"],
 }
 GOLD_OF = {"pe_plain": "pe"}
 

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import rep_fixture as F
+from aln_records import chain_of as _chain_of, compare_pairs_with_reference, record_columns as _record_columns
 from conftest import ROOT, SMALL_PREFIX
 from test_host_pipeline import CASES, UNSET_FLAG, assert_sam_equals_reference_with_its_own_mask, materialise
 
@@ -99,34 +100,6 @@ def _align(rep, pairs, multi_hit=False, est_distance=1500, ws=None):
     return recs, stats[0], cands, (ws.align_reasons() - before).astype(np.int64)[:13]          # ([0..12] are the reasons, include/kart_amd.h)
 
 
-def _record_columns(rep, rec, rlen):
-    """what the SAM line of a record shows, as the columns of the reference's line are compared"""
-    from kart_amd import api
-    if rec["kind"] == api.KG_ALN_UNMAPPED:
-        return (int(rec["flag"]), b"*", 0, 0, b"*", b"*", 0, 0, 0, 0, None)
-    cigar = bytes(rec["cigar"])[:int(rec["cigar_len"])]
-    mate = (b"=", int(rec["mate_pos"]), int(rec["tlen"])) if rec["has_mate"] else (b"*", 0, 0)
-    return (int(rec["flag"]), rep["ix"].contigs[int(rec["chr"])][0].encode(), int(rec["pos"]), int(rec["mapq"]), cigar) + mate + \
-           (int(rec["score"]), int(rec["sub_score"]), rlen - int(rec["score"]))
-
-
-def _line_columns(f):
-    tags = dict(t.split(b":i:") for t in f[11:])
-    return (int(f[1]), f[2], int(f[3]), int(f[4]), f[5], f[6], int(f[7]), int(f[8]), int(tags[b"AS"]), int(tags[b"XS"]), int(tags[b"NM"]) if b"NM" in tags else None)
-
-
-def _chain_of(recs, k):
-    """the records of read k in print order"""
-    from kart_amd import api
-    if recs[k]["kind"] == api.KG_ALN_NONE:
-        return []
-    out, at = [], k
-    while at >= 0:
-        out.append(recs[at])
-        at = int(recs[at]["next"])
-    return out
-
-
 def _pair_key(rep, recs, k):
     """everything the two reads' records say, for the comparison between arrangements"""
     from kart_amd import api
@@ -141,28 +114,7 @@ def _pair_key(rep, recs, k):
 
 def _compare_with_reference(rep, pairs, recs, multi_hit):
     """every read decided on the device against its lines of the reference's SAM; returns the pairs handed back"""
-    from kart_amd import api, synth
-    sam = rep["sam_m"] if multi_hit else rep["sam"]
-    host = []
-    for k, q in enumerate(pairs):
-        kinds = [int(recs[2 * k + m]["kind"]) for m in (0, 1)]
-        assert (kinds[0] == api.KG_ALN_HOST) == (kinds[1] == api.KG_ALN_HOST), q
-        if kinds[0] == api.KG_ALN_HOST:
-            host.append(q)
-            continue
-        for m in (0, 1):
-            read = rep["reads"][2 * q + m]
-            lines = sam.get((rep["names"][q], m), [])
-            chain = _chain_of(recs, 2 * k + m)
-            assert len(chain) == len(lines), (q, m, len(chain), len(lines))
-            for rec, (ln, f) in zip(chain, lines):
-                got, want = _record_columns(rep, rec, len(read)), _line_columns(f)
-                if multi_hit and ln in rep["never"]:
-                    got, want = got[1:], want[1:]
-                assert got == want, (q, m, ln, got, want)
-                if rec["kind"] == api.KG_ALN_MAPPED:
-                    assert f[9] == (synth.revcomp(read) if rec["flip"] else read).tobytes(), (q, m, ln)
-    return host
+    return compare_pairs_with_reference(rep, rep["sam_m"] if multi_hit else rep["sam"], pairs, recs, multi_hit)
 
 
 def _classes(cands, n_pairs):
