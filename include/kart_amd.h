@@ -430,6 +430,17 @@ int   kg_stream_set_tags(kg_stream *s, int tags);
  * earlier setting in place.  Holds for every later kg_stream_map on all lanes; call it while no lane is inside a call.  The call allocates nothing: a
  * batch whose records with the field outgrow a lane's output buffers grows them in kg_stream_map, which knows the batch's size before it makes the text. */
 int   kg_stream_set_read_group(kg_stream *s, const char *id, int len);
+/* The reads that did not map, handed back as the text they came as (on != 0; 0, the default: nothing of the following happens -- no kernel, no buffer).
+ * A UNIT is one read, or (kg_stream_window::paired) one pair.  A unit is selected when every read of it has the unmapped record (FLAG & 4): what
+ * `samtools fastq -f 4` / `-f 12` take from the output; a pair with one mapped mate is not, and with multi_hit a read with any mapped record is mapped.
+ * kg_stream_map then fills kg_stream_result::un .. n_units: per input file the selected units' bytes in input order, each exactly as it lies in the window --
+ * from the first byte of its header line through the line feed of its last line (FASTQ: four lines; FASTA: the header and every line up to the next header or
+ * the end), comments, the '+' line, lower case and '\r' untouched, mate 2 as in the file (not the reverse complement the pipeline holds); both records of
+ * an interleaved pair follow each other in file 0; a file's last line without a line feed gets one.  A unit the device handed back (KG_ALN_HOST) has no
+ * bytes: the caller decides it and makes them.  Holds for every later kg_stream_map on all lanes; call it while no lane is inside a call.  The call
+ * allocates nothing: the first kg_stream_map with the setting on gives its lane the offset tables, and a batch that needs more room for its bytes
+ * than the lane has grows the lane's device and page-locked buffers inside the call (at most the window bytes the batch used). */
+int   kg_stream_set_unmapped(kg_stream *s, int on);
 /* page-locked staging buffer of input file `file` (0 / 1) in lane `lane`, *capacity = max_window bytes */
 char *kg_stream_staging(kg_stream *s, int lane, int file, int64_t *capacity);
 /* staging[file][from, to) -> the lane's device window, asynchronously: a caller reads the next piece meanwhile */
@@ -492,6 +503,11 @@ typedef struct {
 	int64_t n_blocks;
 	const int64_t *block_src;        /* [n_blocks + 1] block i holds sam[block_src[i], block_src[i+1]) (at most 0xff00 bytes) */
 	const int64_t *block_off;        /* [n_blocks + 1] ... and is bgzf[block_off[i], block_off[i+1]) */
+	/* kg_stream_set_unmapped (else NULL / 0): the selected units' input text per file (file 1 only with two_files), page-locked, the lane's */
+	const uint8_t *un[2];
+	int64_t un_bytes[2];
+	const int64_t *un_off[2];        /* [n_units + 1]: unit u is un[f][un_off[f][u], un_off[f][u+1]) -- empty where it is not selected or was handed back */
+	int64_t n_units;                 /* n_reads, or n_reads / 2 for pairs */
 } kg_stream_result;
 /* seeding (FastMode), chaining, the per-read report (kg_align_batch) and the SAM text for the batch kg_stream_parse left in the
  * lane.  The result's arrays belong to the lane: valid until its next kg_stream_parse. */
@@ -533,6 +549,10 @@ typedef struct {
 	/* KG_STREAM_CHECKSUM set (a measurement aid): the SAM text (the BAM records: whatever bytes were made) of the batches summed on the device -- [0] the sum of its bytes, [1] its line feeds
 	 * (exact: both stay far below 2^53) -- so that a run whose output is never copied into file pages still names the text it made; else 0 */
 	double text_checksum[2];
+	/* kg_stream_set_unmapped: [0] un_size + its scans, [1] un_copy (events around each launch, as kernel_ms), and the bytes handed back */
+	double un_kernel_ms[2];
+	int64_t un_kernel_launches[2];
+	double un_bytes;
 } kg_stream_timing_t;
 int   kg_stream_timing(kg_stream *s, kg_stream_timing_t *out, int reset);
 

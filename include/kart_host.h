@@ -65,6 +65,11 @@ typedef struct {
 	 * launches, summed) */
 	int64_t inflate_device_bytes, inflate_host_bytes;
 	double  inflate_device_ms;
+	/* -un / -un2 through the device stream (kg_stream_timing_t): [0] un_size + its scans, [1] un_copy, and the bytes the device handed back (what the host
+	 * made itself -- reads handed back, chunks mapped again, everything outside the stream -- is not counted) */
+	double  un_kernel_ms[2];
+	int64_t un_kernel_launches[2];
+	double  un_bytes;
 } kh_stats_t;
 
 const char *kh_last_error(void);
@@ -79,6 +84,8 @@ int  kh_open(const char *index_prefix, int device, int threads, kh_session **out
  * -md (MD:Z behind XS of every mapped record, which the reference does not print; every other byte of the output is unchanged)
  * and -R '@RG\tID:..' (repeatable: once for all libraries or once per library of -f; "\t" or a real TAB; a header line per distinct -R behind the last @SQ
  * and RG:Z:<ID> as the last field of every record, unmapped ones too; a line that is no read group line fails the call as a bad -bz value does);
+ * -un FILE [-un2 FILE2] (the reads that did not map -- of a pair only when both mates did not -- as the text they came as, in input order; a two-file
+ * library takes both flags, any other -un alone; not with -shard; the alignment output is byte for byte the one without the flags);
  * -i, -t and -gpu are fixed by the session.  Returns 0 on success. */
 int  kh_map(kh_session *s, int argc, const char *const *argv, kh_stats_t *stats);
 /* (measurement aid: with KART_AMD_OUTPUT_NULL=1 in the environment of a kh_map call the text goes to /dev/null instead of the file named by

@@ -56,7 +56,7 @@ ABI_SYMBOLS = (
     "kg_workspace_overflow", "kg_workspace_segment_fallbacks", "kg_workspace_set_profiling", "kg_workspace_set_single_steps", "kg_index_selfcheck", "kg_workspace_kernel_ms", "kg_seed_batch", "kg_candidates_batch", "kg_align_batch", "kg_align_reasons", "kg_seed_batch_device", "kg_nw_batch", "kg_nw_batch_device",
     "kg_fragments_batch", "kg_longread_batch", "kg_longread_reasons",
     "kg_stream_open", "kg_stream_close", "kg_stream_staging", "kg_stream_upload", "kg_stream_parse", "kg_stream_map", "kg_stream_fetch", "kg_stream_fetch_reads", "kg_stream_timing",
-    "kg_stream_group_absent", "kg_stream_group_abort", "kg_stream_set_format", "kg_stream_set_input", "kg_stream_set_tags", "kg_stream_set_read_group",
+    "kg_stream_group_absent", "kg_stream_group_abort", "kg_stream_set_format", "kg_stream_set_input", "kg_stream_set_tags", "kg_stream_set_read_group", "kg_stream_set_unmapped",
     "kg_bgzf_deflate", "kg_bgzf_inflate", "kg_inflater_create", "kg_inflater_reserve", "kg_inflater_src", "kg_inflater_run", "kg_inflater_destroy",
 )
 
@@ -133,16 +133,18 @@ class StreamResult(C.Structure):
     _fields_ = [("n_reads", C.c_int64), ("n_chunks", C.c_int64), ("sam", C.c_void_p), ("sam_bytes", C.c_int64), ("sam_off", C.POINTER(C.c_int64)),
                 ("records", C.c_void_p), ("n_records", C.c_int64), ("chunk_stats", C.c_void_p), ("host_reads", C.POINTER(C.c_int32)), ("n_host_reads", C.c_int64),
                 ("cand_off", C.POINTER(C.c_int64)), ("cands", C.c_void_p), ("cand_seeds", C.c_void_p), ("rec_start", C.POINTER(C.c_uint32) * 2),
-                ("bgzf", C.c_void_p), ("bgzf_bytes", C.c_int64), ("n_blocks", C.c_int64), ("block_src", C.POINTER(C.c_int64)), ("block_off", C.POINTER(C.c_int64))]
+                ("bgzf", C.c_void_p), ("bgzf_bytes", C.c_int64), ("n_blocks", C.c_int64), ("block_src", C.POINTER(C.c_int64)), ("block_off", C.POINTER(C.c_int64)),
+                ("un", C.c_void_p * 2), ("un_bytes", C.c_int64 * 2), ("un_off", C.POINTER(C.c_int64) * 2), ("n_units", C.c_int64)]
 
 
 class StreamTiming(C.Structure):
     _fields_ = [("batches", C.c_int64), ("reads", C.c_int64)] + [(n, C.c_double) for n in ("parse_ms", "seed_ms", "chain_ms", "align_ms", "format_ms", "copy_ms", "search_kernel_ms")] + \
                [("search_kernel_launches", C.c_int64)] + [(n, C.c_double) for n in ("search_useful_bytes", "text_in_bytes", "text_out_bytes", "candidates", "candidate_seeds")] + \
-               [("kernel_ms", C.c_double * 16), ("kernel_launches", C.c_int64 * 16), ("aln_counts", C.c_double * 8), ("text_checksum", C.c_double * 2)]
+               [("kernel_ms", C.c_double * 16), ("kernel_launches", C.c_int64 * 16), ("aln_counts", C.c_double * 8), ("text_checksum", C.c_double * 2),
+                ("un_kernel_ms", C.c_double * 2), ("un_kernel_launches", C.c_int64 * 2), ("un_bytes", C.c_double)]
 
     def as_dict(self):
-        return {n: (list(getattr(self, n)) if n.startswith(("kernel_", "aln_counts")) else getattr(self, n)) for n, _ in self._fields_}
+        return {n: (list(getattr(self, n)) if n.startswith(("kernel_", "aln_counts", "un_kernel_")) else getattr(self, n)) for n, _ in self._fields_}
 
 
 _lib = None
@@ -229,6 +231,7 @@ def load_library() -> C.CDLL:
     L.kg_stream_set_input.argtypes = [C.c_void_p, C.c_int]
     L.kg_stream_set_tags.argtypes = [C.c_void_p, C.c_int]
     L.kg_stream_set_read_group.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+    L.kg_stream_set_unmapped.argtypes = [C.c_void_p, C.c_int]
     L.kg_stream_timing.argtypes = [C.c_void_p, C.POINTER(StreamTiming), C.c_int]
     L.kg_bgzf_deflate.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.kg_bgzf_inflate.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
@@ -639,6 +642,7 @@ class Stream:
         self.h = h
         self.max_window = max_window
         self.last_blocks = None                        # format "bgzf": (bgzf bytes, block_src, block_off) of the last map(); else None
+        self._last_un = {}                             # set_unmapped(True): lane -> [(bytes, offsets) per file] of the lane's last map()
 
     def close(self):
         if self.h:
@@ -672,6 +676,16 @@ class Stream:
         except UnicodeEncodeError as e:
             raise KartAmdError("kg_stream_set_read_group: the ID holds a character outside '!'..'~': %s" % e) from None
         _check(self.lib.kg_stream_set_read_group(self.h, raw, len(raw)), "kg_stream_set_read_group")
+
+    def set_unmapped(self, on: bool):
+        """on: every map() from here on also hands back the input text of the units -- a read, or with paired=True a pair -- whose reads are all
+        unmapped (FLAG & 4), exactly as it lies in the window: last_unmapped().  off (the default): nothing of that happens"""
+        _check(self.lib.kg_stream_set_unmapped(self.h, 1 if on else 0), "kg_stream_set_unmapped")
+
+    def last_unmapped(self, lane: int = 0):
+        """[(bytes, offsets ndarray) per input file] of the lane's last map() under set_unmapped(True): unit u of file f is bytes[offsets[u]:offsets[u + 1]],
+        empty where the unit is not selected or was handed back; an empty list when the setting was off"""
+        return self._last_un.get(lane, [])
 
     def group_absent(self, lane: int, rounds: int):
         """seeding groups: lane `lane` has no batch for `rounds` rounds (< 0: until further notice, 0: it takes part again)"""
@@ -720,6 +734,8 @@ class Stream:
         off = np.ctypeslib.as_array(res.sam_off, shape=(n + 1,)).copy()
         sam = C.string_at(res.sam, res.sam_bytes)
         host = [int(res.host_reads[i]) for i in range(res.n_host_reads)]
+        self._last_un[lane] = [(C.string_at(res.un[f], res.un_bytes[f]) if res.un_bytes[f] else b"", np.ctypeslib.as_array(res.un_off[f], shape=(res.n_units + 1,)).copy())
+                               for f in range(2) if res.un_off[f]]
         self.last_blocks = None
         if res.block_src:
             nb = res.n_blocks
@@ -757,10 +773,11 @@ class HostStats(C.Structure):
                 ("candidates", C.c_double), ("candidate_seeds", C.c_double), ("kernel_ms", C.c_double * 16), ("kernel_launches", C.c_int64 * 16), ("aln_counts", C.c_double * 8),
                 ("lane_seconds", C.c_double * 6), ("lanes", C.c_int32), ("pad2", C.c_int32), ("text_checksum", C.c_double * 2),
                 ("bgzf_device_bytes", C.c_int64), ("bgzf_host_bytes", C.c_int64),
-                ("inflate_device_bytes", C.c_int64), ("inflate_host_bytes", C.c_int64), ("inflate_device_ms", C.c_double)]
+                ("inflate_device_bytes", C.c_int64), ("inflate_host_bytes", C.c_int64), ("inflate_device_ms", C.c_double),
+                ("un_kernel_ms", C.c_double * 2), ("un_kernel_launches", C.c_int64 * 2), ("un_bytes", C.c_double)]
 
     def as_dict(self):
-        return {n: (list(getattr(self, n)) if n.startswith(("kernel_", "stage_", "aln_counts")) else getattr(self, n)) for n, _ in self._fields_}
+        return {n: (list(getattr(self, n)) if n.startswith(("kernel_", "stage_", "aln_counts", "un_kernel_")) else getattr(self, n)) for n, _ in self._fields_}
 
 
 _host_lib = None

@@ -7,6 +7,7 @@
 // the reference's N workers each on their own chunk, src/Mapping.cpp:716-717).
 #include "abi_internal.hpp"
 #include "stream_kernels.hpp"
+#include "un_kernels.hpp"
 #include "bgzf_kernels.hpp"
 
 #include <algorithm>
@@ -32,7 +33,9 @@ enum LaneWord {
 	LW_CHECKSUM = 16,                                  // [16, 18) sam_checksum_kernel's sums (KG_STREAM_CHECKSUM)
 	LW_FETCH_SEEDS = 18,                               // [18, 20) kg_stream_fetch: the candidate seeds' offsets at either end of the reads asked for
 	LW_BGZF = 20,                                      // [20, 24) KG_STREAM_FORMAT_BAM_BGZF: the BGZF launch's control words (BgzfArgs::ctl)
-	LW_WORDS = 24
+	LW_UN_BYTES = 24,                                  // [24, 26) kg_stream_set_unmapped: bytes of the selected units in either file (the scans' totals)
+	LW_UN_CTL = 26,                                    // [26, 29) ... and UnArgs::ctl: the bytes un_copy_kernel wrote per file, spans it did not understand
+	LW_WORDS = 32
 };
 
 struct Lane {
@@ -62,6 +65,16 @@ struct Lane {
 	unsigned long long *d_bgzf_ctl = nullptr;
 	void *d_bgzf_scan = nullptr;
 	size_t bgzf_scan_bytes = 0;
+	// kg_stream_set_unmapped: the tables come with the lane's first kg_stream_map under the setting, the text buffers with the first batch that selects
+	// something, and grow with a batch that needs more (map_un_size / map_un_room)
+	int32_t *d_un_len[2] = {nullptr, nullptr};                 // [max_reads + 8]
+	int64_t *d_un_off[2] = {nullptr, nullptr};
+	uint8_t *d_un[2] = {nullptr, nullptr};
+	int64_t d_un_capacity[2] = {0, 0};
+	unsigned long long *d_un_ctl = nullptr;
+	int64_t *h_un_off[2] = {nullptr, nullptr};                 // page-locked
+	uint8_t *h_un[2] = {nullptr, nullptr};
+	int64_t h_un_capacity[2] = {0, 0};
 	uint8_t *h_bgzf = nullptr;                                 // page-locked, as are the tables
 	int64_t h_bgzf_capacity = 0;
 	int64_t *h_block_src = nullptr, *h_block_off = nullptr;
@@ -163,6 +176,7 @@ struct kg_stream {
 	int format = KG_STREAM_FORMAT_SAM;                 // what kg_stream_map makes of the records (kg_stream_set_format)
 	int input = KG_STREAM_INPUT_FASTQ;                 // what kg_stream_parse takes the text for (kg_stream_set_input)
 	int tags = 0;                                      // KG_STREAM_TAG_*: the optional fields beyond NM / AS / XS (kg_stream_set_tags)
+	bool unmapped = false;                             // kg_stream_map hands the unmapped units' input text back (kg_stream_set_unmapped)
 	// the read group every record carries (kg_stream_set_read_group), in the two forms the kernels copy: "\tRG:Z:<ID>" at d_rg (6 + rg_len bytes) and
 	// 'R' 'G' 'Z' <ID> NUL at d_rg + kRgBamAt (4 + rg_len bytes); rg_len 0: none
 	uint8_t *d_rg = nullptr;
@@ -188,7 +202,12 @@ void free_lane(Lane &l)
 		if (l.d_rec_line[f]) (void)hipFree(l.d_rec_line[f]);
 		if (l.h_text[f]) (void)hipHostFree(l.h_text[f]);
 		if (l.h_rec_hdr[f]) (void)hipHostFree(l.h_rec_hdr[f]);
+		for (void *p : {(void *)l.d_un_len[f], (void *)l.d_un_off[f], (void *)l.d_un[f]})
+			if (p) (void)hipFree(p);
+		for (void *p : {(void *)l.h_un_off[f], (void *)l.h_un[f]})
+			if (p) (void)hipHostFree(p);
 	}
+	if (l.d_un_ctl) (void)hipFree(l.d_un_ctl);
 	for (void *p : {(void *)l.d_meta, (void *)l.d_read_len, l.d_scan, (void *)l.d_sam_len, (void *)l.d_host_list, (void *)l.d_sam_off, (void *)l.d_sam_ctl, (void *)l.d_sam,
 	                (void *)l.d_cuts, (void *)l.d_range_first, (void *)l.d_block_src, (void *)l.d_block_off, (void *)l.d_block_bytes, (void *)l.d_slots, (void *)l.d_bgzf,
 	                (void *)l.d_bgzf_ctl, l.d_bgzf_scan})
@@ -531,6 +550,15 @@ int kg_stream_set_read_group(kg_stream *s, const char *id, int len)
 	return KG_OK;
 }
 
+int kg_stream_set_unmapped(kg_stream *s, int on)
+{
+	if (!s) return fail(KG_ERR_ARG, "kg_stream_set_unmapped: null stream");
+	// (nothing is allocated here: a lane's tables and buffers come, and grow, inside the kg_stream_map calls that need them -- giving every lane new device
+	//  and page-locked buffers in a setter cost a run more than the feature it switched on)
+	s->unmapped = on != 0;
+	return KG_OK;
+}
+
 int kg_stream_set_input(kg_stream *s, int input)
 {
 	if (!s) return fail(KG_ERR_ARG, "kg_stream_set_input: null stream");
@@ -757,6 +785,9 @@ struct MapCall {
 	bool md = false;                                   // the batch's records carry MD:Z (the stream's tags when its text was sized)
 	bool checksum = false;
 	bool bgzf = false;                                 // the BGZF launch of the batch is on the lane's stream (KG_STREAM_FORMAT_BAM_BGZF)
+	bool un = false;                                   // the batch's unmapped units are handed back (the stream's setting when its text was sized)
+	UnArgs u{};
+	int64_t un_bytes[2] = {0, 0};
 	int64_t sam_bytes = 0, n_host = 0, extra = 0;      // bytes of text, reads handed back, extra records of -m
 };
 
@@ -809,6 +840,52 @@ static int map_report(Lane &l, MapCall &m)
 	return KG_OK;
 }
 
+// kg_stream_set_unmapped: which units are handed back and how many bytes each takes in either file; the totals are on their way to the lane's words when
+// this returns (map_size_text's sync brings them over).  The lane's tables are allocated by its first call
+static int map_un_size(kg_stream *s, Lane &l, MapCall &m)
+{
+	hipStream_t st = l.ws->stream;
+	const int nf = l.win.two_files ? 2 : 1;
+	if (l.win.two_files && !l.win.paired) return fail(KG_ERR_ARG, "kg_stream_map: the unmapped reads of two files are handed back as pairs (kg_stream_window::paired)");
+	const size_t slots = (size_t)s->cfg.max_reads + 8;
+	if (!l.d_un_ctl) HIP_TRY(hipMalloc((void **)&l.d_un_ctl, 8 * 4));
+	for (int f = 0; f < nf; ++f) {
+		if (l.d_un_len[f]) continue;
+		HIP_TRY(hipMalloc((void **)&l.d_un_len[f], 4 * slots));
+		HIP_TRY(hipMalloc((void **)&l.d_un_off[f], 8 * slots));
+		HIP_TRY(hipHostMalloc((void **)&l.h_un_off[f], 8 * slots, hipHostMallocDefault));
+	}
+	UnArgs &u = m.u;
+	u.w[0] = m.q.w[0]; u.w[1] = m.q.w[1];
+	u.two_files = m.q.two_files; u.paired = m.q.paired; u.fasta = m.q.fasta;
+	u.n_units = l.win.paired ? m.n / 2 : m.n;
+	u.records = m.a.records;
+	for (int f = 0; f < 2; ++f) { u.un_len[f] = l.d_un_len[f]; u.un_off[f] = l.d_un_off[f]; u.un[f] = l.d_un[f]; u.un_capacity[f] = l.d_un_capacity[f]; }
+	u.ctl = l.d_un_ctl;
+	HIP_TRY(launch_un_size(u, l.d_scan, l.scan_bytes, s->ix->n_cu, st));
+	int64_t *word = l.h_meta + FQM_WORDS;
+	word[LW_UN_BYTES] = word[LW_UN_BYTES + 1] = 0;
+	for (int f = 0; f < nf; ++f) HIP_TRY(hipMemcpyAsync(&word[LW_UN_BYTES + f], l.d_un_off[f] + u.n_units, 8, hipMemcpyDeviceToHost, st));
+	m.un = true;
+	return KG_OK;
+}
+
+// ... and, once the totals are here (the lane's stream is synchronised), room for the bytes: device and page-locked buffers that hold them
+static int map_un_room(Lane &l, MapCall &m)
+{
+	const int64_t *word = l.h_meta + FQM_WORDS;
+	for (int f = 0; f < (l.win.two_files ? 2 : 1); ++f) {
+		const int64_t bytes = m.un_bytes[f] = word[LW_UN_BYTES + f];
+		// (the bytes are a part of the window's: a total beyond it is a table gone wrong, not a size to allocate)
+		if (bytes < 0 || bytes > (l.win.end[f] - l.win.begin[f]) + 1) return fail(KG_ERR_NO_DEVICE, "kg_stream_map: %lld bytes of unmapped reads in a window of %lld", (long long)bytes, (long long)(l.win.end[f] - l.win.begin[f]));
+		const int64_t want = std::max<int64_t>(bytes + bytes / 8, 1 << 16);
+		if (bytes > l.d_un_capacity[f]) HIP_TRY(grow_device(l.d_un[f], l.d_un_capacity[f], want, (size_t)want));
+		if (bytes > l.h_un_capacity[f]) HIP_TRY(grow_pinned(l.h_un[f], l.h_un_capacity[f], want, (size_t)want));
+		m.u.un[f] = l.d_un[f]; m.u.un_capacity[f] = l.d_un_capacity[f];
+	}
+	return KG_OK;
+}
+
 // the size of every read's text (one sync: the totals come over), and buffers that hold the text and, on the host, the batch's candidates
 static int map_size_text(kg_stream *s, Lane &l, MapCall &m)
 {
@@ -842,7 +919,15 @@ static int map_size_text(kg_stream *s, Lane &l, MapCall &m)
 	HIP_TRY(hipMemcpyAsync(&word[LW_TEXT_BYTES], l.d_sam_off + n, 8, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(&word[LW_HOST_READS], l.d_sam_ctl, 8, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(&word[LW_EXTRA_RECORDS], ws->d_aln_ctl + 7, 8, hipMemcpyDeviceToHost, st));
+	if (s->unmapped) {
+		int rc = map_un_size(s, l, m);
+		if (rc != KG_OK) return rc;
+	}
 	HIP_TRY(kgi_sync(ws));
+	if (m.un) {
+		int rc = map_un_room(l, m);
+		if (rc != KG_OK) return rc;
+	}
 	const int64_t sam_bytes = m.sam_bytes = word[LW_TEXT_BYTES];
 	m.n_host = word[LW_HOST_READS];
 	m.extra = m.prm->multi_hit ? std::min<int64_t>(word[LW_EXTRA_RECORDS], m.a.extra_capacity) : 0;
@@ -901,6 +986,7 @@ static int map_format(kg_stream *s, Lane &l, MapCall &m)
 	// measurement aid (bench.py's gpu_pipeline leg): the text summed on the device, for runs that never copy it into file pages (read per call: a session switches it on and off)
 	m.checksum = getenv("KG_STREAM_CHECKSUM") != nullptr;
 	if (m.checksum) HIP_TRY(launch_sam_checksum(m.q, s->ix->n_cu, st));
+	if (m.un && m.un_bytes[0] + m.un_bytes[1] > 0) HIP_TRY(launch_un_copy(m.u, s->ix->n_cu, st));
 	if (s->format == KG_STREAM_FORMAT_BAM_BGZF) {
 		int rc = map_bgzf(s, l, m);
 		if (rc != KG_OK) return rc;
@@ -933,6 +1019,14 @@ static int map_copy_out(Lane &l, MapCall &m, kg_stream_result *out)
 	}
 	if (m.sam_bytes > 0) HIP_TRY(hipMemcpyAsync(l.h_sam, l.d_sam, (size_t)m.sam_bytes, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(l.h_sam_off, l.d_sam_off, 8 * (size_t)(n + 1), hipMemcpyDeviceToHost, st));
+	if (m.un) {
+		// only the selected bytes cross the link; the offsets come whole, as sam_off does
+		for (int f = 0; f < (l.win.two_files ? 2 : 1); ++f) {
+			if (m.un_bytes[f] > 0) HIP_TRY(hipMemcpyAsync(l.h_un[f], l.d_un[f], (size_t)m.un_bytes[f], hipMemcpyDeviceToHost, st));
+			HIP_TRY(hipMemcpyAsync(l.h_un_off[f], l.d_un_off[f], 8 * (size_t)(m.u.n_units + 1), hipMemcpyDeviceToHost, st));
+		}
+		HIP_TRY(hipMemcpyAsync(&word[LW_UN_CTL], l.d_un_ctl, 8 * 3, hipMemcpyDeviceToHost, st));
+	}
 	// the records, candidate offsets, candidates and their seeds stay on the device unless the caller wants them all: it asks for the chunks it needs
 	// (kg_stream_fetch) -- 207 of the 605 bytes per read that used to cross the link
 	const bool all = m.prm->fetch_all != 0;
@@ -955,6 +1049,12 @@ static int map_copy_out(Lane &l, MapCall &m, kg_stream_result *out)
 	HIP_TRY(hipEventRecord(l.ev[6], st));
 	HIP_TRY(kgi_sync(ws));
 	if (word[LW_FORMAT_ERRORS] != 0) return fail(KG_ERR_NO_DEVICE, "kg_stream_map: %lld records were formatted to a size other than the one announced", (long long)word[LW_FORMAT_ERRORS]);
+	if (m.un) {
+		const bool copied = m.un_bytes[0] + m.un_bytes[1] > 0;       // (nothing selected: un_copy_kernel was not launched and its counters stand at zero)
+		for (int f = 0; f < 2; ++f)
+			if (word[LW_UN_CTL + f] != (copied ? m.un_bytes[f] : 0)) return fail(KG_ERR_NO_DEVICE, "kg_stream_map: %lld bytes of unmapped reads were written for file %d, %lld announced", (long long)word[LW_UN_CTL + f], f, (long long)m.un_bytes[f]);
+		if (word[LW_UN_CTL + 2] != 0) return fail(KG_ERR_NO_DEVICE, "kg_stream_map: %lld spans of unmapped reads lie outside their window or buffer", (long long)word[LW_UN_CTL + 2]);
+	}
 	std::sort(l.h_host_list, l.h_host_list + n_host);
 	out->n_reads = n; out->n_chunks = m.n_chunks;
 	out->sam = l.h_sam; out->sam_bytes = m.sam_bytes; out->sam_off = l.h_sam_off;
@@ -966,6 +1066,10 @@ static int map_copy_out(Lane &l, MapCall &m, kg_stream_result *out)
 	if (m.bgzf) {
 		out->bgzf = l.h_bgzf; out->bgzf_bytes = bgzf_bytes; out->n_blocks = n_blocks;
 		out->block_src = l.h_block_src; out->block_off = l.h_block_off;
+	}
+	if (m.un) {
+		for (int f = 0; f < (l.win.two_files ? 2 : 1); ++f) { out->un[f] = l.h_un[f]; out->un_bytes[f] = m.un_bytes[f]; out->un_off[f] = l.h_un_off[f]; }
+		out->n_units = m.u.n_units;
 	}
 	l.have_batch = false;
 	return KG_OK;
@@ -989,6 +1093,7 @@ static void map_account(kg_stream *s, Lane &l, const MapCall &m)
 	t.search_kernel_ms += sk; t.search_kernel_launches += (!m.grouped || m.group_leader) ? 1 : 0; t.search_useful_bytes += useful;
 	t.text_in_bytes += (double)((l.parsed.used[0] - l.win.begin[0]) + (l.win.two_files ? l.parsed.used[1] - l.win.begin[1] : 0));
 	t.text_out_bytes += (double)m.sam_bytes;
+	t.un_bytes += (double)(m.un_bytes[0] + m.un_bytes[1]);
 	t.candidates += (double)m.totals[0]; t.candidate_seeds += (double)m.totals[1];
 	for (int i = 0; i < 8; ++i) t.aln_counts[i] += (double)word[LW_ALN_COUNTS + i];
 	t.text_checksum[0] += (double)(uint64_t)word[LW_CHECKSUM]; t.text_checksum[1] += (double)(uint64_t)word[LW_CHECKSUM + 1];
@@ -997,8 +1102,10 @@ static void map_account(kg_stream *s, Lane &l, const MapCall &m)
 		const int used = ws->kt.used[i];
 		if (!used) continue;
 		ws->kt.used[i] = 0;
-		for (int j = 0; j < used; ++j) t.kernel_ms[i] += elapsed(ws->kt.b[i][j], ws->kt.e[i][j]);
-		t.kernel_launches[i] += used;
+		// (the sixteen slots of kernel_ms, then un_kernel_ms)
+		double &ms = i < 16 ? t.kernel_ms[i] : t.un_kernel_ms[i - 16];
+		for (int j = 0; j < used; ++j) ms += elapsed(ws->kt.b[i][j], ws->kt.e[i][j]);
+		(i < 16 ? t.kernel_launches[i] : t.un_kernel_launches[i - 16]) += used;
 	}
 }
 

@@ -127,6 +127,8 @@ int kh_map(kh_session *s, int argc, const char *const *argv, kh_stats_t *stats)
 		stats->text_checksum[0] = st.device.text_checksum[0]; stats->text_checksum[1] = st.device.text_checksum[1];
 		stats->bgzf_device_bytes = st.bgzf_device_bytes; stats->bgzf_host_bytes = st.bgzf_host_bytes;
 		stats->inflate_device_bytes = st.inflate_device_bytes; stats->inflate_host_bytes = st.inflate_host_bytes; stats->inflate_device_ms = st.inflate_device_ms;
+		for (int i = 0; i < 2; ++i) { stats->un_kernel_ms[i] = st.device.un_kernel_ms[i]; stats->un_kernel_launches[i] = st.device.un_kernel_launches[i]; }
+		stats->un_bytes = st.device.un_bytes;
 	}
 	if (rc == 0) return 0;
 	const std::string why = kart::run_error_message();

@@ -34,6 +34,8 @@ static void usage(const char *prog)
 	fprintf(stdout, "         -m            output multiple alignments\n");
 	fprintf(stdout, "         -md           add MD:Z (mismatches and deletions against the reference) to every mapped record; NM stays read length - AS, not an edit distance\n");
 	fprintf(stdout, "         -R STR        read group header line, e.g. '@RG\\tID:lane1\\tSM:sample'; every record gets RG:Z:<ID>. Once for all libraries, or once per library of -f\n");
+	fprintf(stdout, "         -un FILE      write the reads that did not map to FILE, as they came (FASTQ / FASTA text, input order); of a pair only when both mates are unmapped\n");
+	fprintf(stdout, "         -un2 FILE2    with -f2: the #2 mates of those pairs (then -un holds the #1 mates); not with a device list\n");
 	fprintf(stdout, "         -g INT        max gaps (indels) [5]\n");
 	fprintf(stdout, "         -p            paired-end reads are interlaced in the same file\n");
 	fprintf(stdout, "         -pacbio       pacbio data\n");
@@ -152,6 +154,7 @@ int parse_cli(int argc, char **argv, Options &opt)
 			}
 			opt.read_groups.push_back(line);
 		}
+		else if ((p == "-un" || p == "-un2") && i + 1 < argc) (p == "-un" ? opt.un : opt.un2) = argv[++i];
 		else if (p == "-pair" || p == "-p") opt.paired = true;
 		else if (p == "-v" || p == "--version") { fprintf(stdout, "kart v2.5.6\n\n"); return -1; }
 		else if (p == "-knobs") {          // the environment variables the product reads (host/knobs.inc): none is needed, none changes a result
@@ -174,6 +177,20 @@ int parse_cli(int argc, char **argv, Options &opt)
 		fprintf(stdout, "Error! -R expects to be given once, or once per library (%zu of -f): it was given %zu times\n", opt.files1.size(), opt.read_groups.size());
 		usage(argv[0]);
 		return -2;
+	}
+	{
+		// -un / -un2: one file per input file of a library, and one process (a sharded run would have to merge its shards' files)
+		const bool two_files = !opt.files2.empty();
+		std::string why;
+		if (!opt.un2.empty() && !two_files) why = "-un2 goes with a two-file library (-f A -f2 B); a single-end or interleaved (-p) library takes -un alone";
+		else if (two_files && opt.un.empty() != opt.un2.empty()) why = "a two-file library (-f A -f2 B) takes both -un FILE and -un2 FILE2: records of A go to FILE, records of B to FILE2";
+		else if (!opt.un.empty() && (opt.un == opt.un2 || opt.un == opt.out_name || opt.un2 == opt.out_name)) why = "-un, -un2 and the alignment output name different files";
+		else if (!opt.un.empty() && (opt.devices.size() > 1 || opt.shard_count > 1)) why = "-un / -un2 do not go with a device list (-gpu a,b,..) or -shard: unmapped reads are written by unsharded runs only";
+		if (!why.empty()) {
+			fprintf(stdout, "Error! %s\n", why.c_str());
+			usage(argv[0]);
+			return -2;
+		}
 	}
 	if (!opt.files2.empty() && opt.files1.size() != opt.files2.size()) {
 		fprintf(stdout, "Error! Paired-end reads input numbers do not match!\n");   // reference src/main.cpp:184-190: lists both sets

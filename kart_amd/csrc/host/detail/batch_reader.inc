@@ -543,6 +543,7 @@ void materialise_batch(PoolT &pool, Batch &b, bool by_views, KernelBackend &kern
 		Read &rd = reads[i];
 		rd = Read();
 		rd.name = o.name; rd.seq = o.seq; rd.qual = o.qual; rd.rlen = o.rlen;
+		rd.raw = o.raw;
 	}
 	b.off.assign(reads.size() + 1, 0);
 	for (size_t i = 0; i < reads.size(); ++i) b.off[i + 1] = b.off[i] + reads[i].rlen;

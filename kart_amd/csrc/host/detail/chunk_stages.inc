@@ -128,6 +128,47 @@ void chunk_stage_a(const Ctx &cx, std::vector<Read> &reads, const int64_t *cand_
 	}
 }
 
+// -un / -un2: the input text of the chunk's unmapped units (a read; with -p / -f2 a pair, both mates unmapped), per input file, from the flags stage C has
+// just set.  A read the host mapped is unmapped when it printed the unmapped record (score 0: FLAG & 4, set_single_flag / set_one_mate_flags); one the
+// device decided when its record is that one.  A chunk of the device stream holds the units in hq alone: the device hands the others' bytes back itself
+void chunk_unmapped(const Ctx &cx, std::vector<Read> &reads, ChunkState &ck)
+{
+	for (int f = 0; f < 2; ++f) { ck.un_text[f].clear(); ck.un_host_len[f].clear(); }
+	// (pairs wherever the run is paired and the chunk holds whole pairs -- also where -pacbio maps the mates one by one, chunk_stage_c)
+	const bool pairs = cx.opt.paired && ck.count % 2 == 0;
+	const int step = pairs ? 2 : 1;
+	const bool two_files = cx.un_out[1] != nullptr;
+	size_t k = 0;
+	for (int q = 0; q + step <= ck.count; q += step) {
+		const bool host = k < ck.hq.size() && ck.hq[k] == q;
+		if (!host && ck.stream) continue;
+		bool take = true;
+		const Read *rd[2] = {nullptr, nullptr};
+		for (int t = 0; t < step; ++t) {
+			if (host) {
+				rd[t] = &ck.read_at(reads, k + (size_t)t);
+				take = take && rd[t]->score == 0;
+			} else {
+				rd[t] = &reads[(size_t)(ck.begin + q + t)];
+				const kg_aln_record &rec = ck.recs[ck.begin + q + t];
+				take = take && rec.kind == KG_ALN_UNMAPPED && (rec.flag & 4) != 0;
+			}
+		}
+		if (host) k += (size_t)step;
+		size_t added[2] = {0, 0};
+		for (int t = 0; take && t < step; ++t) {
+			const int f = two_files ? (q + t) & 1 : 0;             // (GetNextChunk: a chunk's even reads come from the first file, its odd ones from the second)
+			std::string &out = ck.un_text[f];
+			const size_t before = out.size();
+			out += rd[t]->raw;
+			if (out.size() > before && out.back() != '\n') out += '\n';       // (the file's last line came without its line feed)
+			added[f] += out.size() - before;
+		}
+		if (ck.stream)
+			for (int f = 0; f < (two_files ? 2 : 1); ++f) ck.un_host_len[f].push_back((uint32_t)added[f]);
+	}
+}
+
 // stage C: report pass 2, final pair check, flags, MAPQ, SAM text
 void chunk_stage_c(const Ctx &cx, std::vector<Read> &reads, ChunkState &ck)
 {
@@ -220,6 +261,7 @@ void chunk_stage_c(const Ctx &cx, std::vector<Read> &reads, ChunkState &ck)
 	else if (cx.opt.bam) bam_encode_chunk(cx, ck.text);
 	ck.text_size = ck.text.size();
 	ck.st.total_reads = ck.count;
+	if (cx.un()) chunk_unmapped(cx, reads, ck);
 	ck.cands.clear(); ck.work.clear();
 	// the reports are spent once the text exists: release them here, on the worker that allocated them, instead of in the
 	// batch destructor on the main thread (400 k small frees per batch, serial)

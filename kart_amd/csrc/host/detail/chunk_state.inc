@@ -42,6 +42,10 @@ struct ChunkState {
 	std::vector<Read> own_reads;
 	std::string own_chars;                           // storage behind own_reads' reverse-complemented mates
 	size_t text_size = 0;                            // bytes of the whole chunk's text
+	// -un / -un2 (chunk_unmapped): the unmapped units' input text per input file -- of the whole chunk, or (stream) of the units in hq alone, un_host_len
+	// bytes per such unit in hq order (0: the unit is not selected)
+	std::string un_text[2];
+	std::vector<uint32_t> un_host_len[2];
 	bool host_read(int q) const { return g_check_align || !recs || recs[begin + q].kind == KG_ALN_HOST || (!force.empty() && force[(size_t)q]); }
 	bool dev_read(int q) const { return recs && recs[begin + q].kind != KG_ALN_HOST && (force.empty() || !force[(size_t)q]); }   // its record stands
 	void list_host_reads()

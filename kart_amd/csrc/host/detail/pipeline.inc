@@ -60,6 +60,12 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 	// but behind two writers.  KART_AMD_NO_EAGER_PARTS=1: as before.
 	const bool eager = deferred && cx.opt.parts && out && !cx.opt.bam && !getenv("KART_AMD_NO_EAGER_PARTS");
 	if (!deferred || eager) writer.reset(new Writer(out, writer_threads, last_writer));
+	// -un / -un2: one more writer per file, fed in chunk order beside the main one (two threads each: in an ordinary run next to nothing goes there)
+	std::unique_ptr<Writer> un_writer[2];
+	for (int f = 0; f < 2; ++f) {
+		if (cx.un_out[f]) un_writer[f].reset(new Writer(cx.un_out[f], 2, true));
+		cx.un_writer[f] = un_writer[f].get();
+	}
 	if (writer && shard.active() && !cx.opt.parts && !getenv("KART_AMD_NO_FILE_TURNS")) writer->take_turns(&shard.rdv->file_turn, shard.rank + 1, &shard.rdv->failed);
 	// small batches first: the estimate moves fastest while the totals are small
 	int64_t batch_chunks = 1;
@@ -193,6 +199,8 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 			bytes_out += (int64_t)ck.text_size;
 			tot.dev_reads += ck.count - ck.n_host; tot.host_reads += ck.n_host;
 			writer->push(std::move(ck.text));
+			for (int f = 0; f < 2; ++f)
+				if (cx.un_writer[f] && !ck.un_text[f].empty()) cx.un_writer[f]->push(std::move(ck.un_text[f]));
 			tot.iPaired += ck.ps.paired;
 			tot.iDistance += ck.ps.distance;
 			st.total_reads += ck.st.total_reads;
@@ -268,6 +276,7 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 			sb->set_format(cx.opt.bam, cx.opt.bam && cx.opt.bz_device);      // (the stream is the session's: a -o run may follow a -bo run, a -bz host run a -bz device one)
 			sb->set_tags(cx.opt.md);                    // (... and a run with -md one without)
 			sb->set_read_group(cx.opt.read_group_id(cx.lib));      // (... and a library with a read group one without, or with another)
+			sb->set_unmapped(cx.un());                  // (... and a run with -un one without)
 			sb->set_input(!cx.fastq);                   // (... and a FASTQ library a FASTA one)
 			Options &o = const_cast<Options &>(cx.opt);
 			const int64_t keep = o.batch_reads;
@@ -455,6 +464,10 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 	}
 	double td = now_s();
 	if (writer) finish_writer(*writer, tot);
+	for (int f = 0; f < 2; ++f) {
+		if (un_writer[f]) un_writer[f]->finish();
+		cx.un_writer[f] = nullptr;
+	}
 	tot.t_drain += now_s() - td;
 	if (shard.active()) shard.rdv->written[shard.rank].store(1);
 }

@@ -10,6 +10,7 @@ struct Input {
 	size_t cap = 0;
 	std::vector<char> gzbuf;
 	bool ended = false;            // the device stream took the library to its end: nothing is left for this reader
+	bool keep_raw = false;         // -un / -un2: an entry keeps the bytes of the lines it consumed (OwnedRead::raw)
 	~Input() { close(); }
 	void close()
 	{
@@ -33,6 +34,7 @@ std::string_view header_view(const char *buf, int len)  // IdentifyHeaderBegPos/
 // a read owned by the reader itself (getline()/gzgets() paths)
 struct OwnedRead {
 	std::string name, seq, qual;
+	std::string raw;               // Input::keep_raw: the lines of the entry as they were read, one after the other
 	int rlen = 0;
 };
 
@@ -44,16 +46,18 @@ bool next_entry_plain(Input &in, bool fastq, OwnedRead &rd)
 	ssize_t len = getline(&in.line, &in.cap, in.fp);
 	if (len == -1) return false;
 	rd.name.assign(header_view(in.line, (int)len));
+	if (in.keep_raw) rd.raw.assign(in.line, (size_t)len);
 	if (fastq) {
 		ssize_t sl = getline(&in.line, &in.cap, in.fp);
 		if (sl == -1) { rd.rlen = 0; return true; }
 		rd.rlen = (int)sl - 1;
 		rd.seq.assign(in.line, (size_t)rd.rlen);
+		if (in.keep_raw) rd.raw.append(in.line, (size_t)sl);
 		// The reference reads the '+' line and the quality line into the same buffer without looking at the results (:73): in a file
 		// that ends inside a record the "qualities" are whatever the buffer still holds -- the '+' line, or the bases themselves
 		ssize_t held = sl, got;
-		if ((got = getline(&in.line, &in.cap, in.fp)) != -1) held = got;
-		if ((got = getline(&in.line, &in.cap, in.fp)) != -1) held = got;
+		if ((got = getline(&in.line, &in.cap, in.fp)) != -1) { held = got; if (in.keep_raw) rd.raw.append(in.line, (size_t)got); }
+		if ((got = getline(&in.line, &in.cap, in.fp)) != -1) { held = got; if (in.keep_raw) rd.raw.append(in.line, (size_t)got); }
 		rd.qual.assign(in.line, (size_t)std::min<ssize_t>(held, rd.rlen));
 		rd.qual.resize((size_t)rd.rlen, '\0');
 		rd.qual = std::string(rd.qual.c_str());   // the reference treats it as a C string
@@ -63,6 +67,7 @@ bool next_entry_plain(Input &in, bool fastq, OwnedRead &rd)
 			len = getline(&in.line, &in.cap, in.fp);
 			if (len == -1) break;
 			if (in.line[0] == '>') { fseek(in.fp, 0 - len, SEEK_CUR); break; }
+			if (in.keep_raw) rd.raw.append(in.line, (size_t)len);
 			in.line[len - 1] = '\0';
 			seq += in.line;
 		}
@@ -81,17 +86,18 @@ bool next_entry_gz(Input &in, bool fastq, bool pacbio, OwnedRead &rd)  // gzGetN
 	if (gzgets(in.gz, buf, buf_size) == NULL) return false;
 	int len = (int)strlen(buf);
 	std::string name(header_view(buf, len));
+	if (in.keep_raw) rd.raw.assign(buf, (size_t)len);
 	if (!name.empty() && (buf[0] == '@' || buf[0] == '>')) {
 		rd.name = name;
 		// none of the three further gzgets() results is looked at (:168-175): in a stream that ends inside a record the buffer keeps
 		// the last line that did arrive, and that is what the reference takes for the bases / the qualities
-		gzgets(in.gz, buf, buf_size);
+		if (gzgets(in.gz, buf, buf_size) != NULL && in.keep_raw) rd.raw.append(buf);
 		rd.rlen = (int)strlen(buf) - 1;
 		if (rd.rlen < 0) rd.rlen = 0;
 		rd.seq.assign(buf, (size_t)rd.rlen);
 		if (fastq) {
-			gzgets(in.gz, buf, buf_size);
-			gzgets(in.gz, buf, buf_size);
+			if (gzgets(in.gz, buf, buf_size) != NULL && in.keep_raw) rd.raw.append(buf);
+			if (gzgets(in.gz, buf, buf_size) != NULL && in.keep_raw) rd.raw.append(buf);
 			rd.qual.assign(buf, std::min<size_t>(strlen(buf), (size_t)rd.rlen));
 		}
 	}
@@ -218,6 +224,7 @@ struct MappedFile {
 struct RecView {
 	const char *hdr, *seq, *qual;
 	int hdr_len, rlen, qual_len;
+	int raw_len;  // bytes from hdr through the last line the entry consumed (-un / -un2: Read::raw)
 	bool flip;    // mate 2 of a pair: stored reverse-complemented (src/GetData.cpp:125-135)
 };
 
@@ -227,7 +234,7 @@ bool view_next(MappedFile &f, RecView &v)
 	const char *p;
 	ssize_t len = f.line(p);
 	if (len == -1) return false;
-	v.hdr = p; v.hdr_len = (int)len;
+	v.hdr = p; v.hdr_len = (int)len; v.raw_len = (int)len;
 	// A file that ends inside a record: the reference reads the remaining lines into one buffer without looking at the results
 	// (src/GetData.cpp:73, :168-175), so a line that never came is whatever the buffer still held -- `held` below.  getline()'s
 	// caller does check the sequence line (:69); gzgets()'s does not and takes the header line for the bases.
@@ -242,6 +249,7 @@ bool view_next(MappedFile &f, RecView &v)
 	if ((got = f.line(p)) != -1) { held = p; held_len = got; }
 	if ((got = f.line(p)) != -1) { held = p; held_len = got; }
 	v.qual = held; v.qual_len = (int)held_len;
+	v.raw_len = (int)(f.data + f.pos - v.hdr);           // (the lines lie one behind the other: through the last one that came)
 	return true;
 }
 
@@ -267,6 +275,7 @@ struct FastaView {
 	int hdr_len = 0, rlen = 0;
 	bool joined = false;
 	size_t seq_pos = 0;           // where the first line behind the header starts
+	size_t raw_len = 0;           // bytes from hdr through the last line the entry consumed (-un / -un2)
 };
 
 bool fasta_view_next(MappedFile &f, FastaView &v)
@@ -275,12 +284,13 @@ bool fasta_view_next(MappedFile &f, FastaView &v)
 	ssize_t len = f.line(p);
 	if (len == -1) return false;
 	v = FastaView();
-	v.hdr = p; v.hdr_len = (int)len; v.seq_pos = f.pos;
+	v.hdr = p; v.hdr_len = (int)len; v.seq_pos = f.pos; v.raw_len = (size_t)len;
 	if (f.gz_lines) {
 		if (header_view(p, (int)len).empty() || (p[0] != '@' && p[0] != '>')) return true;
 		ssize_t sl = f.line(p);
 		if (sl == -1) { p = v.hdr; sl = len; }            // (the buffer still holds the header line, next_entry_gz)
 		v.seq = p; v.rlen = std::max(0, (int)sl - 1);
+		v.raw_len = (size_t)(f.data + f.pos - v.hdr);
 		return true;
 	}
 	int lines = 0;
@@ -293,6 +303,7 @@ bool fasta_view_next(MappedFile &f, FastaView &v)
 		v.rlen += (int)sl - 1;
 	}
 	v.joined = lines > 1;
+	v.raw_len = (size_t)(f.data + f.pos - v.hdr);
 	return true;
 }
 
@@ -324,6 +335,7 @@ void views_of_indexed_records(PoolT &pool, const MappedFile &f, std::vector<RecV
 			v.hdr = data + l0; v.hdr_len = (int)(l1 - l0);
 			v.seq = data + l1; v.rlen = (int)(l2 - l1) - 1;
 			v.qual = data + l3; v.qual_len = (int)(l4 - l3);
+			v.raw_len = (int)(l4 - l0);
 			v.flip = false;
 		}
 	});
@@ -336,6 +348,7 @@ void materialise(const RecView &v, Read &rd, char *enc)
 {
 	rd = Read();
 	rd.name = header_view(v.hdr, v.hdr_len);
+	rd.raw = std::string_view(v.hdr, (size_t)v.raw_len);      // (a view: nothing is copied; read only under -un / -un2)
 	rd.rlen = v.rlen;
 	int ql = std::min(v.qual_len, v.rlen);
 	const char *z = ql > 0 ? (const char *)memchr(v.qual, '\0', (size_t)ql) : nullptr;

@@ -294,6 +294,7 @@ void stream_own_reads_fasta(const Ctx &cx, const Source &src, const StreamBatch 
 		const bool flip = cx.opt.paired && (r & 1);
 		Read &rd = ck.own_reads[k];
 		rd.name = header_view(v.hdr, v.hdr_len);
+		rd.raw = std::string_view(v.hdr, v.raw_len);
 		rd.rlen = v.rlen;
 		if (!v.joined && !flip) { rd.seq = std::string_view(v.seq ? v.seq : "", (size_t)v.rlen); continue; }
 		char *dst = &ck.own_chars[at];
@@ -330,6 +331,7 @@ void stream_own_reads_fastq(const Ctx &cx, const Source &src, const StreamBatch 
 		const RecView &v = views[k];
 		Read &rd = ck.own_reads[k];
 		rd.name = header_view(v.hdr, v.hdr_len);
+		rd.raw = std::string_view(v.hdr, (size_t)v.raw_len);
 		rd.rlen = v.rlen;
 		int ql = std::min(v.qual_len, v.rlen);
 		const char *z = ql > 0 ? (const char *)memchr(v.qual, '\0', (size_t)ql) : nullptr;
@@ -371,6 +373,28 @@ void stream_chunk_pieces(const StreamBatch &b, const ChunkState &ck, std::vector
 	}
 	const int64_t end = ck.begin + ck.count;
 	if (off[end] > off[from]) { out.push_back(TextPiece{sam + off[from], (size_t)(off[end] - off[from])}); total += out.back().n; }
+}
+
+// -un / -un2: the chunk's unmapped reads of input file f as pieces, the same way: the device's bytes (kg_stream_result::un, per unit) between the units
+// the host mapped, and the host's own bytes for those (consecutive parts of ck.un_text[f], ck.un_host_len[f] per unit in hq order)
+void stream_chunk_un_pieces(const StreamBatch &b, const ChunkState &ck, int f, std::vector<TextPiece> &out, size_t &total)
+{
+	const int64_t *off = b.res.un_off[f];
+	const char *un = (const char *)b.res.un[f];
+	const int step = ck.paired ? 2 : 1;
+	int64_t from = ck.begin / step;
+	size_t piece = 0;
+	total = 0;
+	for (size_t k = 0; k < ck.hq.size(); k += (size_t)step) {
+		const int64_t u = (ck.begin + ck.hq[k]) / step;
+		if (off[u] > off[from]) { out.push_back(TextPiece{un + off[from], (size_t)(off[u] - off[from])}); total += out.back().n; }
+		const uint32_t n = ck.un_host_len[f][piece++];
+		if (n) { out.push_back(TextPiece{nullptr, n}); total += n; }
+		from = u + 1;
+		// (a forced pair's device bytes are skipped: the host decided it again)
+	}
+	const int64_t end = (ck.begin + ck.count) / step;
+	if (off[end] > off[from]) { out.push_back(TextPiece{un + off[from], (size_t)(off[end] - off[from])}); total += out.back().n; }
 }
 
 // the reads of a chunk the host stages map: the device's list restricted to the chunk, plus the forced pairs
@@ -616,6 +640,8 @@ void add_timing(kg_stream_timing_t &into, const kg_stream_timing_t &from)
 	for (int i = 0; i < 16; ++i) { into.kernel_ms[i] += from.kernel_ms[i]; into.kernel_launches[i] += from.kernel_launches[i]; }
 	for (int i = 0; i < 8; ++i) into.aln_counts[i] += from.aln_counts[i];
 	into.text_checksum[0] += from.text_checksum[0]; into.text_checksum[1] += from.text_checksum[1];
+	for (int i = 0; i < 2; ++i) { into.un_kernel_ms[i] += from.un_kernel_ms[i]; into.un_kernel_launches[i] += from.un_kernel_launches[i]; }
+	into.un_bytes += from.un_bytes;
 }
 
 // One library's run through the stream: K lane threads (lane_thread) feed the commit (the caller's thread) through `feed`.
@@ -897,9 +923,17 @@ struct StreamRun {
 	// every chunk's text to where it goes: a deferred shard's list, the packer (-bo) or the writer
 	void emit_chunks(StreamBatch &b)
 	{
-		b.writes_pending.store((int)b.chunks.size());
+		// (-un / -un2: every chunk is pushed to each of those writers as well, and each push counts)
+		const int n_un = cx.un_writer[0] ? (cx.un_writer[1] ? 2 : 1) : 0;
+		b.writes_pending.store((int)b.chunks.size() * (1 + n_un));
 		for (size_t c = 0; c < b.chunks.size(); ++c) {
 			ChunkState &ck = b.chunks[c];
+			for (int f = 0; f < n_un; ++f) {
+				std::vector<TextPiece> un_pieces;
+				size_t un_total = 0;
+				stream_chunk_un_pieces(b, ck, f, un_pieces, un_total);
+				cx.un_writer[f]->push_pieces(std::move(un_pieces), un_total, std::move(ck.un_text[f]), &b.writes_pending, &feed.mu, &feed.cv);
+			}
 			std::vector<TextPiece> pieces;
 			size_t total = 0;
 			stream_chunk_pieces(b, ck, pieces, total);

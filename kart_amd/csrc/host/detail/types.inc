@@ -151,6 +151,8 @@ struct Read {
 	// views into the mapped input file, or into the batch's own storage (reverse-complemented mates, the
 	// getline()/gzgets() readers); no per-read allocation
 	std::string_view name, seq, qual;
+	// -un / -un2 (empty otherwise): the record as it lies in the input text, from the first byte of its header line through the last line the reader took for it
+	std::string_view raw;
 	bool qual_rev = false;     // `qual` is the file's bytes of a mate that is held reversed: the held string is its reverse
 	int rlen = 0;
 	int mapq = 0, score = 0, sub_score = 0, can_num = 0, best = 0;
@@ -174,6 +176,10 @@ struct Ctx {
 	bool frag_service = false;     // -pacbio: GenerateNormalPairAlignment runs on the device in one call per batch (KernelBackend::fragments_batch)
 	std::map<std::string_view, int> bam_ref_id;   // -bo: contig name -> reference id
 	size_t lib = 0;                // the library being mapped: its place in Options::files1
+	// -un / -un2: where the unmapped reads of either input file go (null: nowhere), and the writers of the library being mapped (map_library)
+	FILE *un_out[2] = {nullptr, nullptr};
+	class Writer *un_writer[2] = {nullptr, nullptr};
+	bool un() const { return un_out[0] != nullptr; }
 	std::string rg_field;          // -R: "\tRG:Z:<ID>" of the library being mapped, the last field of every record it prints; empty: none
 	const char *refseq() const { return ref.seq.get(); }
 };

@@ -82,6 +82,10 @@ public:
 	{
 		if (kg_stream_set_read_group(s_, id.empty() ? nullptr : id.data(), (int)id.size()) != KG_OK) die("kg_stream_set_read_group");
 	}
+	void set_unmapped(bool on) override
+	{
+		if (kg_stream_set_unmapped(s_, on ? 1 : 0) != KG_OK) die("kg_stream_set_unmapped");
+	}
 	kg_stream *handle() const { return s_; }
 
 private:

@@ -189,6 +189,18 @@ int run_mapping(const Options &opt, const RefData &ref, KernelBackend &kern, FIL
 	}
 	Ctx cx{opt, ref, kern, kern.min_seed_len()};
 	cx.frag_service = opt.pacbio && kern.has_fragments();
+	// -un / -un2: created here, empty, whatever the libraries hold; every library's writers continue where the last one's stopped
+	struct UnFiles {
+		FILE *fp[2] = {nullptr, nullptr};
+		~UnFiles() { for (FILE *f : fp) if (f) fclose(f); }
+	} un_files;
+	for (int f = 0; f < 2; ++f) {
+		const std::string &name = f ? opt.un2 : opt.un;
+		if (name.empty()) continue;
+		un_files.fp[f] = fopen(name.c_str(), "w+");
+		if (!un_files.fp[f]) { fprintf(stderr, "Error! Cannot open file [%s]\n", name.c_str()); return 1; }
+	}
+	if (un_files.fp[0]) { cx.un_out[0] = un_files.fp[0]; cx.un_out[1] = un_files.fp[1]; }
 	Options &o = const_cast<Options &>(opt);
 	RunTotals tot;
 	// one process per GPU (shard.inc): this process maps shard_rank of shard_count chunk ranges of the library
@@ -224,6 +236,7 @@ int run_mapping(const Options &opt, const RefData &ref, KernelBackend &kern, FIL
 		cx.rg_field = opt.read_groups.empty() ? std::string() : "\tRG:Z:" + opt.read_group_id(lib);
 		Source src;
 		Input &in1 = src.in1, &in2 = src.in2;
+		in1.keep_raw = in2.keep_raw = cx.un();
 		bool want_fast = !gz && cx.fastq && !getenv("KART_AMD_NO_MMAP");
 		if (gz) in1.gz = gzopen(f1.c_str(), "rb"); else in1.fp = fopen(f1.c_str(), "r");
 		bool sep = false;

@@ -41,6 +41,10 @@ struct Options {
 	// parse_cli.  Every record of a library's reads carries RG:Z:<ID> of its line as its last field, and the header one line per distinct -R
 	std::vector<std::string> read_groups;
 	std::string read_group_id(size_t lib) const;    // the ID: value of library lib's line; empty without -R
+	// -un FILE [-un2 FILE2]: the reads that did not map, written back as the text they came as (a single-end read whose record is unmapped; a pair when BOTH
+	// mates are: `samtools fastq -f 4` / `-f 12`), in input order, every library appended.  A two-file library (-f A -f2 B) takes both: records of A to
+	// un, of B to un2; parse_cli rejects anything else.  Empty: nothing is written
+	std::string un, un2;
 	bool fz_device = false;   // -fz device: the members of bgzip-ped read files are inflated on the device (default: host, zlib on the -t threads)
 	int device = 0;
 	std::vector<int> devices;       // -gpu a,b,c: one process per listed device, the input sharded between them
@@ -107,6 +111,8 @@ struct StreamBackend {
 	virtual void set_tags(bool md) { (void)md; }
 	// the read group every record carries as its last field from here on (kg_stream_set_read_group); empty: none; while no lane works
 	virtual void set_read_group(const std::string &id) { (void)id; }
+	// map() fills the result's un .. n_units from here on: the input text of the units whose reads are all unmapped (kg_stream_set_unmapped); while no lane works
+	virtual void set_unmapped(bool on) { (void)on; }
 };
 
 // The fragment pairs of one chunk whose alignment GenerateNormalPairAlignment (src/tools.cpp:142-223) is to produce -- 8-mer partition,
