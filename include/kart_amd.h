@@ -267,6 +267,37 @@ int  kg_align_batch(kg_workspace *ws, const int64_t *chunk_off, const uint8_t *c
                     int est_distance, int max_insert, int max_gaps, int multi_hit, int unset_flag,
                     const kg_aln_record **records, kg_chunk_stats *chunk_stats);
 
+/* ---- a tally of the records a batch prints (kg_stream_set_stats, kg_tally_records) ------------------------------------ */
+/* One row of KG_STATS_WORDS uint32_t per chunk: what `samtools flagstat` / `stats` would count over the chunk's output records.  A record counts when its
+ * kind is KG_ALN_UNMAPPED or KG_ALN_MAPPED -- a read's own record and, with multi_hit, every record chained behind it through `next`, all for the chunk
+ * of the read; KG_ALN_NONE prints nothing and KG_ALN_HOST is the caller's to count.  "mapped" below is FLAG & 4 == 0, as in the output.
+ *   [KG_STATS_RECORDS]            records
+ *   [KG_STATS_FLAG0 + b]          records with FLAG bit b set, b = 0 .. 11 (0x1 .. 0x800)
+ *   [KG_STATS_PROPER]             FLAG & 1, FLAG & 2, FLAG & 4 == 0
+ *   [KG_STATS_BOTH_MAPPED]        FLAG & 1, FLAG & 12 == 0
+ *   [KG_STATS_SINGLETON]          FLAG & 1, FLAG & 4 == 0, FLAG & 8
+ *   [KG_STATS_CIGAR0 + 2 k]       mapped records' CIGARs: summed lengths of the operations of class k, [.. + 2 k + 1] their number; k = 0 .. 4 for
+ *                                 M, I, D, S and any other letter (a KG_ALN_CIGAR_POOLED text is not in the record and counts nothing)
+ *   [KG_STATS_MAPQ0 + q]          mapped records with MAPQ q, q = 0 .. 63; above 63 in bin 63 (an unmapped-kind record prints MAPQ 0)
+ *   [KG_STATS_ISIZE0 + d]         records with FLAG & 1, a mate (has_mate: RNEXT "=") and TLEN d > 0, d = 1 .. 2048; from 2048 on in bin 2048 */
+#define KG_STATS_RECORDS      0
+#define KG_STATS_FLAG0        1
+#define KG_STATS_FLAG_BITS    12
+#define KG_STATS_PROPER       13
+#define KG_STATS_BOTH_MAPPED  14
+#define KG_STATS_SINGLETON    15
+#define KG_STATS_CIGAR0       16
+#define KG_STATS_CIGAR_CLASSES 5
+#define KG_STATS_MAPQ0        26
+#define KG_STATS_MAPQ_BINS    64
+#define KG_STATS_ISIZE0       90
+#define KG_STATS_ISIZE_MAX    2048
+#define KG_STATS_WORDS        (KG_STATS_ISIZE0 + KG_STATS_ISIZE_MAX + 1)
+/* The tally of host records: records[n_records] are uploaded to the current device, tallied by the kernel kg_stream_map runs under kg_stream_set_stats
+ * and rows[n_chunks][KG_STATS_WORDS] copied out.  The first n_reads records are the reads' own; chunk_off[n_chunks + 1] (ascending, within [0, n_reads])
+ * names the reads of each chunk; a `next` outside [n_reads, n_records) ends its chain.  Needs a device, no index and no stream. */
+int  kg_tally_records(const kg_aln_record *records, int64_t n_records, int64_t n_reads, const int64_t *chunk_off, int n_chunks, uint32_t *rows);
+
 /* ---- the per-read report of long reads (-pacbio) on the device ------------------------------------------------------- */
 /* What ReadMapping()'s bPacBioData branch does per read between chaining and the SAM text (src/Mapping.cpp:513-530), for the reads
  * of the batch the last kg_seed_batch (KG_MODE_SENSITIVE | KG_INPUT_ASCII) + kg_candidates_batch (pacbio != 0) calls on this
@@ -441,6 +472,12 @@ int   kg_stream_set_read_group(kg_stream *s, const char *id, int len);
  * allocates nothing: the first kg_stream_map with the setting on gives its lane the offset tables, and a batch that needs more room for its bytes
  * than the lane has grows the lane's device and page-locked buffers inside the call (at most the window bytes the batch used). */
 int   kg_stream_set_unmapped(kg_stream *s, int on);
+/* A tally of the records each batch prints (on != 0; 0, the default: nothing of the following happens -- no kernel, no buffer): kg_stream_map then runs
+ * stats_tally_kernel over the batch's final records and fills kg_stream_result::chunk_tally, one row per chunk (KG_STATS_*, above).  Records of kind
+ * KG_ALN_HOST are not in a row: the caller counts what it prints for them, and recounts a chunk it maps again from the records that stand.  Holds for
+ * every later kg_stream_map on all lanes; call it while no lane is inside a call.  The call allocates nothing: a lane's device rows and page-locked
+ * table come with its first kg_stream_map under the setting and grow with a batch of more chunks. */
+int   kg_stream_set_stats(kg_stream *s, int on);
 /* page-locked staging buffer of input file `file` (0 / 1) in lane `lane`, *capacity = max_window bytes */
 char *kg_stream_staging(kg_stream *s, int lane, int file, int64_t *capacity);
 /* staging[file][from, to) -> the lane's device window, asynchronously: a caller reads the next piece meanwhile */
@@ -508,6 +545,7 @@ typedef struct {
 	int64_t un_bytes[2];
 	const int64_t *un_off[2];        /* [n_units + 1]: unit u is un[f][un_off[f][u], un_off[f][u+1]) -- empty where it is not selected or was handed back */
 	int64_t n_units;                 /* n_reads, or n_reads / 2 for pairs */
+	const uint32_t *chunk_tally;     /* kg_stream_set_stats (else NULL): [n_chunks][KG_STATS_WORDS], page-locked, the lane's */
 } kg_stream_result;
 /* seeding (FastMode), chaining, the per-read report (kg_align_batch) and the SAM text for the batch kg_stream_parse left in the
  * lane.  The result's arrays belong to the lane: valid until its next kg_stream_parse. */
@@ -553,6 +591,10 @@ typedef struct {
 	double un_kernel_ms[2];
 	int64_t un_kernel_launches[2];
 	double un_bytes;
+	/* kg_stream_set_stats: stats_tally_kernel (events around each launch, as kernel_ms) and the bytes of rows copied to the host */
+	double stats_kernel_ms;
+	int64_t stats_kernel_launches;
+	double stats_bytes;
 } kg_stream_timing_t;
 int   kg_stream_timing(kg_stream *s, kg_stream_timing_t *out, int reset);
 

@@ -70,6 +70,10 @@ typedef struct {
 	double  un_kernel_ms[2];
 	int64_t un_kernel_launches[2];
 	double  un_bytes;
+	/* -stats through the device stream (kg_stream_timing_t): stats_tally_kernel's milliseconds and launches, and the bytes of rows it handed back */
+	double  stats_kernel_ms;
+	int64_t stats_kernel_launches;
+	double  stats_bytes;
 } kh_stats_t;
 
 const char *kh_last_error(void);
@@ -86,6 +90,8 @@ int  kh_open(const char *index_prefix, int device, int threads, kh_session **out
  * and RG:Z:<ID> as the last field of every record, unmapped ones too; a line that is no read group line fails the call as a bad -bz value does);
  * -un FILE [-un2 FILE2] (the reads that did not map -- of a pair only when both mates did not -- as the text they came as, in input order; a two-file
  * library takes both flags, any other -un alone; not with -shard; the alignment output is byte for byte the one without the flags);
+ * -stats FILE (a summary of the records the run printed -- counts per FLAG bit, MAPQ, insert size and CIGAR operation, TAB-separated text -- written when
+ * the run is over; not with -shard; the alignment output is byte for byte the one without the flag);
  * -i, -t and -gpu are fixed by the session.  Returns 0 on success. */
 int  kh_map(kh_session *s, int argc, const char *const *argv, kh_stats_t *stats);
 /* (measurement aid: with KART_AMD_OUTPUT_NULL=1 in the environment of a kh_map call the text goes to /dev/null instead of the file named by

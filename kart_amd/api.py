@@ -48,6 +48,10 @@ ALN_DT = np.dtype([("pos", "<i8"), ("mate_pos", "<i8"), ("kind", "<i4"), ("flag"
 CHUNK_STATS_DT = np.dtype([("paired", "<i8"), ("distance", "<i8"), ("lo", "<i8"), ("hi", "<i8"), ("unmapped", "<i4"), ("unique", "<i4"),
                            ("host_pairs", "<i4"), ("rescue_wanted", "<i4")])
 assert ALN_DT.itemsize == 112 and CHUNK_STATS_DT.itemsize == 48
+# a row of the records' tally (kg_stream_set_stats, kg_tally_records): uint32 words, the layout of include/kart_amd.h
+KG_STATS_RECORDS, KG_STATS_FLAG0, KG_STATS_FLAG_BITS, KG_STATS_PROPER, KG_STATS_BOTH_MAPPED, KG_STATS_SINGLETON = 0, 1, 12, 13, 14, 15
+KG_STATS_CIGAR0, KG_STATS_CIGAR_CLASSES, KG_STATS_MAPQ0, KG_STATS_MAPQ_BINS, KG_STATS_ISIZE0, KG_STATS_ISIZE_MAX = 16, 5, 26, 64, 90, 2048
+KG_STATS_WORDS = KG_STATS_ISIZE0 + KG_STATS_ISIZE_MAX + 1
 
 # every symbol include/kart_amd.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = (
@@ -57,6 +61,7 @@ ABI_SYMBOLS = (
     "kg_fragments_batch", "kg_longread_batch", "kg_longread_reasons",
     "kg_stream_open", "kg_stream_close", "kg_stream_staging", "kg_stream_upload", "kg_stream_parse", "kg_stream_map", "kg_stream_fetch", "kg_stream_fetch_reads", "kg_stream_timing",
     "kg_stream_group_absent", "kg_stream_group_abort", "kg_stream_set_format", "kg_stream_set_input", "kg_stream_set_tags", "kg_stream_set_read_group", "kg_stream_set_unmapped",
+    "kg_stream_set_stats", "kg_tally_records",
     "kg_bgzf_deflate", "kg_bgzf_inflate", "kg_inflater_create", "kg_inflater_reserve", "kg_inflater_src", "kg_inflater_run", "kg_inflater_destroy",
 )
 
@@ -134,14 +139,16 @@ class StreamResult(C.Structure):
                 ("records", C.c_void_p), ("n_records", C.c_int64), ("chunk_stats", C.c_void_p), ("host_reads", C.POINTER(C.c_int32)), ("n_host_reads", C.c_int64),
                 ("cand_off", C.POINTER(C.c_int64)), ("cands", C.c_void_p), ("cand_seeds", C.c_void_p), ("rec_start", C.POINTER(C.c_uint32) * 2),
                 ("bgzf", C.c_void_p), ("bgzf_bytes", C.c_int64), ("n_blocks", C.c_int64), ("block_src", C.POINTER(C.c_int64)), ("block_off", C.POINTER(C.c_int64)),
-                ("un", C.c_void_p * 2), ("un_bytes", C.c_int64 * 2), ("un_off", C.POINTER(C.c_int64) * 2), ("n_units", C.c_int64)]
+                ("un", C.c_void_p * 2), ("un_bytes", C.c_int64 * 2), ("un_off", C.POINTER(C.c_int64) * 2), ("n_units", C.c_int64),
+                ("chunk_tally", C.POINTER(C.c_uint32))]
 
 
 class StreamTiming(C.Structure):
     _fields_ = [("batches", C.c_int64), ("reads", C.c_int64)] + [(n, C.c_double) for n in ("parse_ms", "seed_ms", "chain_ms", "align_ms", "format_ms", "copy_ms", "search_kernel_ms")] + \
                [("search_kernel_launches", C.c_int64)] + [(n, C.c_double) for n in ("search_useful_bytes", "text_in_bytes", "text_out_bytes", "candidates", "candidate_seeds")] + \
                [("kernel_ms", C.c_double * 16), ("kernel_launches", C.c_int64 * 16), ("aln_counts", C.c_double * 8), ("text_checksum", C.c_double * 2),
-                ("un_kernel_ms", C.c_double * 2), ("un_kernel_launches", C.c_int64 * 2), ("un_bytes", C.c_double)]
+                ("un_kernel_ms", C.c_double * 2), ("un_kernel_launches", C.c_int64 * 2), ("un_bytes", C.c_double),
+                ("stats_kernel_ms", C.c_double), ("stats_kernel_launches", C.c_int64), ("stats_bytes", C.c_double)]
 
     def as_dict(self):
         return {n: (list(getattr(self, n)) if n.startswith(("kernel_", "aln_counts", "un_kernel_")) else getattr(self, n)) for n, _ in self._fields_}
@@ -232,6 +239,8 @@ def load_library() -> C.CDLL:
     L.kg_stream_set_tags.argtypes = [C.c_void_p, C.c_int]
     L.kg_stream_set_read_group.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
     L.kg_stream_set_unmapped.argtypes = [C.c_void_p, C.c_int]
+    L.kg_stream_set_stats.argtypes = [C.c_void_p, C.c_int]
+    L.kg_tally_records.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]
     L.kg_stream_timing.argtypes = [C.c_void_p, C.POINTER(StreamTiming), C.c_int]
     L.kg_bgzf_deflate.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     L.kg_bgzf_inflate.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
@@ -643,6 +652,7 @@ class Stream:
         self.max_window = max_window
         self.last_blocks = None                        # format "bgzf": (bgzf bytes, block_src, block_off) of the last map(); else None
         self._last_un = {}                             # set_unmapped(True): lane -> [(bytes, offsets) per file] of the lane's last map()
+        self._last_stats = {}                          # set_stats(True): lane -> the rows of the lane's last map()
 
     def close(self):
         if self.h:
@@ -686,6 +696,16 @@ class Stream:
         """[(bytes, offsets ndarray) per input file] of the lane's last map() under set_unmapped(True): unit u of file f is bytes[offsets[u]:offsets[u + 1]],
         empty where the unit is not selected or was handed back; an empty list when the setting was off"""
         return self._last_un.get(lane, [])
+
+    def set_stats(self, on: bool):
+        """on: every map() from here on also tallies the batch's final records per chunk on the device (flags, MAPQ, insert sizes, CIGAR operations;
+        the records of reads handed back are not among them): last_stats().  off (the default): nothing of that happens"""
+        _check(self.lib.kg_stream_set_stats(self.h, 1 if on else 0), "kg_stream_set_stats")
+
+    def last_stats(self, lane: int = 0):
+        """ndarray (n_chunks, KG_STATS_WORDS) uint32 of the lane's last map() under set_stats(True) -- row c tallies chunk c, the KG_STATS_* layout --;
+        None when the setting was off (kg_stream_result::chunk_tally is NULL)"""
+        return self._last_stats.get(lane)
 
     def group_absent(self, lane: int, rounds: int):
         """seeding groups: lane `lane` has no batch for `rounds` rounds (< 0: until further notice, 0: it takes part again)"""
@@ -736,6 +756,7 @@ class Stream:
         host = [int(res.host_reads[i]) for i in range(res.n_host_reads)]
         self._last_un[lane] = [(C.string_at(res.un[f], res.un_bytes[f]) if res.un_bytes[f] else b"", np.ctypeslib.as_array(res.un_off[f], shape=(res.n_units + 1,)).copy())
                                for f in range(2) if res.un_off[f]]
+        self._last_stats[lane] = np.ctypeslib.as_array(res.chunk_tally, shape=(int(res.n_chunks), KG_STATS_WORDS)).copy() if res.chunk_tally else None
         self.last_blocks = None
         if res.block_src:
             nb = res.n_blocks
@@ -747,6 +768,19 @@ class Stream:
         t = StreamTiming()
         _check(self.lib.kg_stream_timing(self.h, C.byref(t), 1 if reset else 0), "kg_stream_timing")
         return t.as_dict()
+
+
+def tally_records(records, n_reads: int, chunk_off):
+    """kg_tally_records: the tally of `records` (ALN_DT; the first n_reads are the reads' own, the rest are reached through `next`) per chunk --
+    chunk c holds reads chunk_off[c] .. chunk_off[c + 1] -- by the kernel Stream.map() runs under set_stats(True).
+    Returns ndarray (n_chunks, KG_STATS_WORDS) uint32.  Needs a device, no index."""
+    lib = load_library()
+    recs = np.ascontiguousarray(records, dtype=ALN_DT)
+    off = np.ascontiguousarray(chunk_off, dtype=np.int64)
+    rows = np.zeros((max(0, len(off) - 1), KG_STATS_WORDS), dtype=np.uint32)
+    _check(lib.kg_tally_records(_ptr(recs) if len(recs) else None, len(recs), int(n_reads), _ptr(off), len(off) - 1, _ptr(rows) if rows.size else _ptr(np.zeros(1, np.uint32))),
+           "kg_tally_records")
+    return rows
 
 
 def apply_ops(s1: bytes, s2: bytes, ops: np.ndarray):
@@ -774,7 +808,8 @@ class HostStats(C.Structure):
                 ("lane_seconds", C.c_double * 6), ("lanes", C.c_int32), ("pad2", C.c_int32), ("text_checksum", C.c_double * 2),
                 ("bgzf_device_bytes", C.c_int64), ("bgzf_host_bytes", C.c_int64),
                 ("inflate_device_bytes", C.c_int64), ("inflate_host_bytes", C.c_int64), ("inflate_device_ms", C.c_double),
-                ("un_kernel_ms", C.c_double * 2), ("un_kernel_launches", C.c_int64 * 2), ("un_bytes", C.c_double)]
+                ("un_kernel_ms", C.c_double * 2), ("un_kernel_launches", C.c_int64 * 2), ("un_bytes", C.c_double),
+                ("stats_kernel_ms", C.c_double), ("stats_kernel_launches", C.c_int64), ("stats_bytes", C.c_double)]
 
     def as_dict(self):
         return {n: (list(getattr(self, n)) if n.startswith(("kernel_", "stage_", "aln_counts", "un_kernel_")) else getattr(self, n)) for n, _ in self._fields_}

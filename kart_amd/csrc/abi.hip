@@ -527,7 +527,23 @@ void kg_workspace_destroy(kg_workspace *ws)
 {
 	if (!ws) return;
 	(void)hipSetDevice(ws->ix->device);
-	if (ws->stream) { (void)hipStreamSynchronize(ws->stream); (void)hipStreamDestroy(ws->stream); }
+	if (ws->stream) {
+		(void)hipStreamSynchronize(ws->stream);
+		// The index's NW scratches whose last kernels ran on this stream are free from here on, and their events must not outlive it: an event last
+		// recorded on a destroyed stream was later queried by nw_acquire (the scratch still counted as busy), and the runtime answered with whatever
+		// the stream's memory had become -- "an event last recorded in a capturing stream" on the first kg_stream_map of a new stream, depending on
+		// what ran in the process before.  nw_acquire gives such a scratch a fresh event.
+		{
+			std::lock_guard<std::mutex> lock(ws->ix->nw_mu);
+			for (NwScratch *s : ws->ix->nw_pool) {
+				if (s->last_stream != ws->stream || s->pending) continue;
+				s->busy = false;
+				s->last_stream = nullptr;
+				if (s->done) { (void)hipEventDestroy(s->done); s->done = nullptr; }
+			}
+		}
+		(void)hipStreamDestroy(ws->stream);
+	}
 	kgi_long_release(ws);
 	for (int i = 0; i < kg_workspace::kRing; ++i) {
 		if (ws->ring_cands[i]) (void)hipHostFree(ws->ring_cands[i]);
@@ -983,6 +999,7 @@ static int nw_acquire(kg_index *ix, size_t list_words, size_t dir_words, hipStre
 		HIP_TRY(hipMalloc((void **)&pick->dir, dir_words * 4));
 		pick->dir_words = dir_words;
 	}
+	if (!pick->done) HIP_TRY(hipEventCreateWithFlags(&pick->done, hipEventDisableTiming));     // (kg_workspace_destroy took it with the stream it was recorded on)
 	pick->busy = true;
 	pick->pending = true;
 	pick->last_stream = st;

@@ -8,6 +8,7 @@
 #include "abi_internal.hpp"
 #include "stream_kernels.hpp"
 #include "un_kernels.hpp"
+#include "stats_kernels.hpp"
 #include "bgzf_kernels.hpp"
 
 #include <algorithm>
@@ -75,6 +76,10 @@ struct Lane {
 	int64_t *h_un_off[2] = {nullptr, nullptr};                 // page-locked
 	uint8_t *h_un[2] = {nullptr, nullptr};
 	int64_t h_un_capacity[2] = {0, 0};
+	// kg_stream_set_stats: one row per chunk, on the device and page-locked; both come with the lane's first kg_stream_map under the setting and grow with a
+	// batch of more chunks (map_tally)
+	uint32_t *d_tally = nullptr, *h_tally = nullptr;
+	int64_t tally_capacity = 0, h_tally_capacity = 0;          // chunks
 	uint8_t *h_bgzf = nullptr;                                 // page-locked, as are the tables
 	int64_t h_bgzf_capacity = 0;
 	int64_t *h_block_src = nullptr, *h_block_off = nullptr;
@@ -177,6 +182,7 @@ struct kg_stream {
 	int input = KG_STREAM_INPUT_FASTQ;                 // what kg_stream_parse takes the text for (kg_stream_set_input)
 	int tags = 0;                                      // KG_STREAM_TAG_*: the optional fields beyond NM / AS / XS (kg_stream_set_tags)
 	bool unmapped = false;                             // kg_stream_map hands the unmapped units' input text back (kg_stream_set_unmapped)
+	bool stats = false;                                // kg_stream_map tallies the batch's records per chunk (kg_stream_set_stats)
 	// the read group every record carries (kg_stream_set_read_group), in the two forms the kernels copy: "\tRG:Z:<ID>" at d_rg (6 + rg_len bytes) and
 	// 'R' 'G' 'Z' <ID> NUL at d_rg + kRgBamAt (4 + rg_len bytes); rg_len 0: none
 	uint8_t *d_rg = nullptr;
@@ -208,6 +214,8 @@ void free_lane(Lane &l)
 			if (p) (void)hipHostFree(p);
 	}
 	if (l.d_un_ctl) (void)hipFree(l.d_un_ctl);
+	if (l.d_tally) (void)hipFree(l.d_tally);
+	if (l.h_tally) (void)hipHostFree(l.h_tally);
 	for (void *p : {(void *)l.d_meta, (void *)l.d_read_len, l.d_scan, (void *)l.d_sam_len, (void *)l.d_host_list, (void *)l.d_sam_off, (void *)l.d_sam_ctl, (void *)l.d_sam,
 	                (void *)l.d_cuts, (void *)l.d_range_first, (void *)l.d_block_src, (void *)l.d_block_off, (void *)l.d_block_bytes, (void *)l.d_slots, (void *)l.d_bgzf,
 	                (void *)l.d_bgzf_ctl, l.d_bgzf_scan})
@@ -559,6 +567,14 @@ int kg_stream_set_unmapped(kg_stream *s, int on)
 	return KG_OK;
 }
 
+int kg_stream_set_stats(kg_stream *s, int on)
+{
+	if (!s) return fail(KG_ERR_ARG, "kg_stream_set_stats: null stream");
+	// (nothing is allocated here, as in kg_stream_set_unmapped: a lane's rows come, and grow, inside the kg_stream_map calls that need them)
+	s->stats = on != 0;
+	return KG_OK;
+}
+
 int kg_stream_set_input(kg_stream *s, int input)
 {
 	if (!s) return fail(KG_ERR_ARG, "kg_stream_set_input: null stream");
@@ -788,6 +804,7 @@ struct MapCall {
 	bool un = false;                                   // the batch's unmapped units are handed back (the stream's setting when its text was sized)
 	UnArgs u{};
 	int64_t un_bytes[2] = {0, 0};
+	bool tally = false;                                // the batch's records are tallied (the stream's setting when the kernel was launched)
 	int64_t sam_bytes = 0, n_host = 0, extra = 0;      // bytes of text, reads handed back, extra records of -m
 };
 
@@ -979,6 +996,28 @@ static int map_bgzf(kg_stream *s, Lane &l, MapCall &m)
 	return KG_OK;
 }
 
+// kg_stream_set_stats: the tally of the batch's final records, a row per chunk (the records are final once the report stage is through: the text
+// kernels only read them).  The lane's rows are allocated by its first call and grow with a batch of more chunks
+static int map_tally(Lane &l, MapCall &m)
+{
+	if (m.n_chunks > l.tally_capacity) {
+		const int64_t want = m.n_chunks + m.n_chunks / 2 + 64;
+		HIP_TRY(grow_device(l.d_tally, l.tally_capacity, want, 4 * (size_t)KG_STATS_WORDS * (size_t)want));
+	}
+	if (m.n_chunks > l.h_tally_capacity) {
+		const int64_t want = m.n_chunks + m.n_chunks / 2 + 64;
+		HIP_TRY(grow_pinned(l.h_tally, l.h_tally_capacity, want, 4 * (size_t)KG_STATS_WORDS * (size_t)want));
+	}
+	StatsArgs t{};
+	t.records = m.a.records;
+	t.n_reads = m.n; t.n_records = m.n + m.extra;
+	t.chunk_off = m.a.chunk_off; t.n_chunks = m.n_chunks;
+	t.rows = l.d_tally;
+	HIP_TRY(launch_stats_tally(t, l.ws->stream));
+	m.tally = true;
+	return KG_OK;
+}
+
 static int map_format(kg_stream *s, Lane &l, MapCall &m)
 {
 	hipStream_t st = l.ws->stream;
@@ -987,6 +1026,10 @@ static int map_format(kg_stream *s, Lane &l, MapCall &m)
 	m.checksum = getenv("KG_STREAM_CHECKSUM") != nullptr;
 	if (m.checksum) HIP_TRY(launch_sam_checksum(m.q, s->ix->n_cu, st));
 	if (m.un && m.un_bytes[0] + m.un_bytes[1] > 0) HIP_TRY(launch_un_copy(m.u, s->ix->n_cu, st));
+	if (s->stats) {
+		int rc = map_tally(l, m);
+		if (rc != KG_OK) return rc;
+	}
 	if (s->format == KG_STREAM_FORMAT_BAM_BGZF) {
 		int rc = map_bgzf(s, l, m);
 		if (rc != KG_OK) return rc;
@@ -1034,6 +1077,7 @@ static int map_copy_out(Lane &l, MapCall &m, kg_stream_result *out)
 	if (all) HIP_TRY(hipMemcpyAsync(l.h_records, a.records, sizeof(kg_aln_record) * (size_t)(n + extra), hipMemcpyDeviceToHost, st));
 	else if (extra > 0) HIP_TRY(hipMemcpyAsync(l.h_records + n, a.records + n, sizeof(kg_aln_record) * (size_t)extra, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(l.h_chunk_stats, ws->d_chunk_stats, sizeof(kg_chunk_stats) * (size_t)m.n_chunks, hipMemcpyDeviceToHost, st));
+	if (m.tally) HIP_TRY(hipMemcpyAsync(l.h_tally, l.d_tally, 4 * (size_t)KG_STATS_WORDS * (size_t)m.n_chunks, hipMemcpyDeviceToHost, st));
 	if (all) HIP_TRY(hipMemcpyAsync(l.h_cand_off, ws->d_cand_off, 8 * (size_t)(n + 1), hipMemcpyDeviceToHost, st));
 	// the candidates travel with every batch: the reads handed back need them, and so does a pair the caller maps again because its
 	// speculated EstDistance did not hold
@@ -1071,6 +1115,7 @@ static int map_copy_out(Lane &l, MapCall &m, kg_stream_result *out)
 		for (int f = 0; f < (l.win.two_files ? 2 : 1); ++f) { out->un[f] = l.h_un[f]; out->un_bytes[f] = m.un_bytes[f]; out->un_off[f] = l.h_un_off[f]; }
 		out->n_units = m.u.n_units;
 	}
+	if (m.tally) out->chunk_tally = l.h_tally;
 	l.have_batch = false;
 	return KG_OK;
 }
@@ -1094,6 +1139,7 @@ static void map_account(kg_stream *s, Lane &l, const MapCall &m)
 	t.text_in_bytes += (double)((l.parsed.used[0] - l.win.begin[0]) + (l.win.two_files ? l.parsed.used[1] - l.win.begin[1] : 0));
 	t.text_out_bytes += (double)m.sam_bytes;
 	t.un_bytes += (double)(m.un_bytes[0] + m.un_bytes[1]);
+	if (m.tally) t.stats_bytes += 4.0 * KG_STATS_WORDS * (double)m.n_chunks;
 	t.candidates += (double)m.totals[0]; t.candidate_seeds += (double)m.totals[1];
 	for (int i = 0; i < 8; ++i) t.aln_counts[i] += (double)word[LW_ALN_COUNTS + i];
 	t.text_checksum[0] += (double)(uint64_t)word[LW_CHECKSUM]; t.text_checksum[1] += (double)(uint64_t)word[LW_CHECKSUM + 1];
@@ -1102,10 +1148,10 @@ static void map_account(kg_stream *s, Lane &l, const MapCall &m)
 		const int used = ws->kt.used[i];
 		if (!used) continue;
 		ws->kt.used[i] = 0;
-		// (the sixteen slots of kernel_ms, then un_kernel_ms)
-		double &ms = i < 16 ? t.kernel_ms[i] : t.un_kernel_ms[i - 16];
+		// (the sixteen slots of kernel_ms, then un_kernel_ms, then stats_kernel_ms)
+		double &ms = i < 16 ? t.kernel_ms[i] : i == KT_STATS ? t.stats_kernel_ms : t.un_kernel_ms[i - 16];
 		for (int j = 0; j < used; ++j) ms += elapsed(ws->kt.b[i][j], ws->kt.e[i][j]);
-		(i < 16 ? t.kernel_launches[i] : t.un_kernel_launches[i - 16]) += used;
+		(i < 16 ? t.kernel_launches[i] : i == KT_STATS ? t.stats_kernel_launches : t.un_kernel_launches[i - 16]) += used;
 	}
 }
 
@@ -1214,6 +1260,37 @@ int kg_stream_fetch(kg_stream *s, int lane, int64_t first, int64_t count)
 	if (c1 > c0) HIP_TRY(hipMemcpyAsync(l.h_cands + c0, ws->d_dense_cands + c0, sizeof(kg_candidate) * (size_t)(c1 - c0), hipMemcpyDeviceToHost, st));
 	if (s1 > s0) HIP_TRY(hipMemcpyAsync(l.h_cand_seeds + s0, ws->d_dense_seeds + s0, sizeof(kg_seed) * (size_t)(s1 - s0), hipMemcpyDeviceToHost, st));
 	HIP_TRY(kgi_sync(ws));
+	return KG_OK;
+}
+
+int kg_tally_records(const kg_aln_record *records, int64_t n_records, int64_t n_reads, const int64_t *chunk_off, int n_chunks, uint32_t *rows)
+{
+	if (!chunk_off || !rows || n_chunks < 0 || n_reads < 0 || n_records < n_reads || (n_records > 0 && !records)) return fail(KG_ERR_ARG, "kg_tally_records: bad argument");
+	for (int c = 0; c < n_chunks; ++c)
+		if (chunk_off[c] < 0 || chunk_off[c + 1] < chunk_off[c] || chunk_off[c + 1] > n_reads)
+			return fail(KG_ERR_ARG, "kg_tally_records: chunk %d is reads [%lld, %lld) of %lld", c, (long long)chunk_off[c], (long long)chunk_off[c + 1], (long long)n_reads);
+	if (n_chunks == 0) return KG_OK;
+	// (device buffers of this call alone, freed on every way out)
+	struct Buffers {
+		kg_aln_record *records = nullptr;
+		int64_t *chunk_off = nullptr;
+		uint32_t *rows = nullptr;
+		~Buffers() { for (void *p : {(void *)records, (void *)chunk_off, (void *)rows}) if (p) (void)hipFree(p); }
+	} d;
+	const size_t row_bytes = 4 * (size_t)KG_STATS_WORDS * (size_t)n_chunks;
+	HIP_TRY(hipMalloc((void **)&d.records, sizeof(kg_aln_record) * (size_t)std::max<int64_t>(n_records, 1)));
+	HIP_TRY(hipMalloc((void **)&d.chunk_off, 8 * (size_t)(n_chunks + 1)));
+	HIP_TRY(hipMalloc((void **)&d.rows, row_bytes));
+	if (n_records > 0) HIP_TRY(hipMemcpy(d.records, records, sizeof(kg_aln_record) * (size_t)n_records, hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(d.chunk_off, chunk_off, 8 * (size_t)(n_chunks + 1), hipMemcpyHostToDevice));
+	StatsArgs t{};
+	t.records = d.records;
+	t.n_reads = n_reads; t.n_records = n_records;
+	t.chunk_off = d.chunk_off; t.n_chunks = n_chunks;
+	t.rows = d.rows;
+	HIP_TRY(launch_stats_tally(t, nullptr));
+	HIP_TRY(hipDeviceSynchronize());
+	HIP_TRY(hipMemcpy(rows, d.rows, row_bytes, hipMemcpyDeviceToHost));
 	return KG_OK;
 }
 

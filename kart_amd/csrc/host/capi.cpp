@@ -101,6 +101,11 @@ int kh_map(kh_session *s, int argc, const char *const *argv, kh_stats_t *stats)
 			return fail("kh_map: cannot open [%s]", opt.out_name.c_str());
 		}
 	}
+	FILE *stats_file = nullptr;
+	if (!kart::open_stats(opt, stats_file)) {
+		if (out) fclose(out);
+		return fail("kh_map: cannot open [%s]", opt.stats.c_str());
+	}
 	kart::Stats st;
 	auto now = []() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; };
 	double t0 = now();
@@ -108,6 +113,8 @@ int kh_map(kh_session *s, int argc, const char *const *argv, kh_stats_t *stats)
 	if (rc != 0 && opt.shard_count > 1) kart::shard_mark_failed(opt.rendezvous, opt.shard_rank);     // the other shards stop waiting for this one
 	double t1 = now();
 	if (out) fclose(out);
+	if (rc != 0 && stats_file) fclose(stats_file);
+	else if (rc == 0 && !kart::write_stats(st, stats_file)) return fail("kh_map: cannot write [%s]", opt.stats.c_str());
 	if (getenv("KART_AMD_VERBOSE")) fprintf(stdout, "kh_map: run_mapping %.3f s (its own mapping seconds %.3f), closing the output %.3f s\n", t1 - t0, st.map_seconds, now() - t1);
 	if (stats) {
 		stats->total_reads = st.total_reads; stats->unmapped = st.unmapped; stats->unique = st.unique; stats->paired = st.paired;
@@ -129,6 +136,7 @@ int kh_map(kh_session *s, int argc, const char *const *argv, kh_stats_t *stats)
 		stats->inflate_device_bytes = st.inflate_device_bytes; stats->inflate_host_bytes = st.inflate_host_bytes; stats->inflate_device_ms = st.inflate_device_ms;
 		for (int i = 0; i < 2; ++i) { stats->un_kernel_ms[i] = st.device.un_kernel_ms[i]; stats->un_kernel_launches[i] = st.device.un_kernel_launches[i]; }
 		stats->un_bytes = st.device.un_bytes;
+		stats->stats_kernel_ms = st.device.stats_kernel_ms; stats->stats_kernel_launches = st.device.stats_kernel_launches; stats->stats_bytes = st.device.stats_bytes;
 	}
 	if (rc == 0) return 0;
 	const std::string why = kart::run_error_message();

@@ -36,6 +36,7 @@ static void usage(const char *prog)
 	fprintf(stdout, "         -R STR        read group header line, e.g. '@RG\\tID:lane1\\tSM:sample'; every record gets RG:Z:<ID>. Once for all libraries, or once per library of -f\n");
 	fprintf(stdout, "         -un FILE      write the reads that did not map to FILE, as they came (FASTQ / FASTA text, input order); of a pair only when both mates are unmapped\n");
 	fprintf(stdout, "         -un2 FILE2    with -f2: the #2 mates of those pairs (then -un holds the #1 mates); not with a device list\n");
+	fprintf(stdout, "         -stats FILE   write a summary of the output records to FILE: counts per FLAG bit, MAPQ, insert size and CIGAR operation; not with a device list\n");
 	fprintf(stdout, "         -g INT        max gaps (indels) [5]\n");
 	fprintf(stdout, "         -p            paired-end reads are interlaced in the same file\n");
 	fprintf(stdout, "         -pacbio       pacbio data\n");
@@ -155,6 +156,14 @@ int parse_cli(int argc, char **argv, Options &opt)
 			opt.read_groups.push_back(line);
 		}
 		else if ((p == "-un" || p == "-un2") && i + 1 < argc) (p == "-un" ? opt.un : opt.un2) = argv[++i];
+		else if (p == "-stats") {
+			if (i + 1 >= argc || argv[i + 1][0] == '\0') {
+				fprintf(stdout, "Error! -stats expects a file name behind it\n");
+				usage(argv[0]);
+				return -2;
+			}
+			opt.stats = argv[++i];
+		}
 		else if (p == "-pair" || p == "-p") opt.paired = true;
 		else if (p == "-v" || p == "--version") { fprintf(stdout, "kart v2.5.6\n\n"); return -1; }
 		else if (p == "-knobs") {          // the environment variables the product reads (host/knobs.inc): none is needed, none changes a result
@@ -186,6 +195,17 @@ int parse_cli(int argc, char **argv, Options &opt)
 		else if (two_files && opt.un.empty() != opt.un2.empty()) why = "a two-file library (-f A -f2 B) takes both -un FILE and -un2 FILE2: records of A go to FILE, records of B to FILE2";
 		else if (!opt.un.empty() && (opt.un == opt.un2 || opt.un == opt.out_name || opt.un2 == opt.out_name)) why = "-un, -un2 and the alignment output name different files";
 		else if (!opt.un.empty() && (opt.devices.size() > 1 || opt.shard_count > 1)) why = "-un / -un2 do not go with a device list (-gpu a,b,..) or -shard: unmapped reads are written by unsharded runs only";
+		if (!why.empty()) {
+			fprintf(stdout, "Error! %s\n", why.c_str());
+			usage(argv[0]);
+			return -2;
+		}
+	}
+	if (!opt.stats.empty()) {
+		// -stats: a file of its own, and one process (a sharded run would have to join its shards' tallies)
+		std::string why;
+		if (opt.stats == opt.out_name || opt.stats == opt.un || opt.stats == opt.un2) why = "-stats, the alignment output, -un and -un2 name different files";
+		else if (opt.devices.size() > 1 || opt.shard_count > 1) why = "-stats does not go with a device list (-gpu a,b,..) or -shard: the summary is written by unsharded runs only";
 		if (!why.empty()) {
 			fprintf(stdout, "Error! %s\n", why.c_str());
 			usage(argv[0]);
@@ -302,9 +322,12 @@ int cli_main(int argc, char **argv, KernelBackend *(*make_backend)(const Options
 	if (opt.shard_count > 1 && opt.rendezvous.empty()) { fprintf(stdout, "Error! -shard needs -rendezvous FILE\n"); return 1; }
 	time_t t0 = time(NULL);
 	Stats st;
+	FILE *stats_file = nullptr;
+	if (!open_stats(opt, stats_file)) return 1;          // (before the index is loaded and anything is mapped)
 	const bool launcher = opt.devices.size() > 1 && opt.shard_count == 1;
 	rc = launcher ? run_sharded(opt, make_backend, st) : run_one(opt, make_backend, st, false);
-	if (rc != 0) return rc;
+	if (rc != 0) { if (stats_file) fclose(stats_file); return rc; }
+	if (!write_stats(st, stats_file)) { fprintf(stderr, "Error! Cannot write file [%s]\n", opt.stats.c_str()); return 1; }
 	bool paired = opt.paired || !opt.files2.empty();
 	if (opt.shard_count > 1) {     // one shard of a run someone else coordinates: that process reports the totals
 		if (getenv("KART_AMD_VERBOSE")) fprintf(stdout, "shard %d/%d: %lld reads, mapping seconds %.3f, re-mapped chunks %lld\n", opt.shard_rank, opt.shard_count, (long long)st.total_reads, st.map_seconds, (long long)st.respeculated);

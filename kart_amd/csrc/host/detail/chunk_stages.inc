@@ -169,10 +169,38 @@ void chunk_unmapped(const Ctx &cx, std::vector<Read> &reads, ChunkState &ck)
 	}
 }
 
+// -stats: the device's share of a stream chunk's tally (the host's own reads, ck.hq, are counted where they are printed).  The rule of stage A's first lines:
+// nothing of the chunk is mapped again -- the device's row as it is (it leaves out the reads handed back); otherwise a recount of the records that stand,
+// each with the records chained behind it (-m), so that a chunk mapped again counts once, under its final records
+void chunk_device_tally(ChunkState &ck)
+{
+	if (!ck.tally || !ck.stream || !ck.recs) return;
+	if (ck.force.empty()) {
+		if (ck.dev_tally) ck.tally->add_row(ck.dev_tally);
+		return;
+	}
+	const int64_t n_reads = ck.n_records_reads;
+	for (int q = 0; q < ck.count; ++q) {
+		if (!ck.dev_read(q)) continue;
+		int64_t at = ck.begin + q;
+		for (int64_t step = 0; step <= ck.n_records - n_reads; ++step) {
+			ck.tally->add(ck.recs[at]);
+			const int64_t next = ck.recs[at].next;
+			if (next < n_reads || next >= ck.n_records) break;
+			at = next;
+		}
+	}
+}
+
 // stage C: report pass 2, final pair check, flags, MAPQ, SAM text
 void chunk_stage_c(const Ctx &cx, std::vector<Read> &reads, ChunkState &ck)
 {
 	const size_t nh = ck.hq.size();
+	if (cx.stats) {
+		if (!ck.tally) ck.tally = std::make_shared<Tally>();
+		ck.tally->clear();
+	}
+	TallyInto tally_into(cx.stats ? ck.tally.get() : nullptr);
 	{ Section sec(3);
 	// pass 2 reads the text at the fragment pairs' positions again (random addresses in 6.2 GB for hg38, long after the plan touched
 	// them): ask for the first lines of the pairs of the read two places ahead
@@ -262,6 +290,7 @@ void chunk_stage_c(const Ctx &cx, std::vector<Read> &reads, ChunkState &ck)
 	ck.text_size = ck.text.size();
 	ck.st.total_reads = ck.count;
 	if (cx.un()) chunk_unmapped(cx, reads, ck);
+	if (cx.stats) chunk_device_tally(ck);
 	ck.cands.clear(); ck.work.clear();
 	// the reports are spent once the text exists: release them here, on the worker that allocated them, instead of in the
 	// batch destructor on the main thread (400 k small frees per batch, serial)

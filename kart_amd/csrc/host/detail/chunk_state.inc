@@ -46,6 +46,11 @@ struct ChunkState {
 	// bytes per such unit in hq order (0: the unit is not selected)
 	std::string un_text[2];
 	std::vector<uint32_t> un_host_len[2];
+	// -stats (null otherwise): the tally of the records the chunk prints -- what the host printed (the printer's record sites, sam.inc) plus, for a chunk of
+	// the device stream, the device's share (chunk_device_tally): its row dev_tally when every record of it stands, else a recount of those that do
+	std::shared_ptr<Tally> tally;
+	const uint32_t *dev_tally = nullptr;             // the chunk's row of kg_stream_result::chunk_tally
+	int64_t n_records_reads = 0, n_records = 0;      // ... and the reads and records of its batch (the -m chains lie in [reads, records))
 	bool host_read(int q) const { return g_check_align || !recs || recs[begin + q].kind == KG_ALN_HOST || (!force.empty() && force[(size_t)q]); }
 	bool dev_read(int q) const { return recs && recs[begin + q].kind != KG_ALN_HOST && (force.empty() || !force[(size_t)q]); }   // its record stands
 	void list_host_reads()
@@ -76,6 +81,7 @@ std::atomic<int64_t> g_check_bad{0}, g_check_n{0};
 void check_record_text(const Ctx &cx, const ChunkState &ck, const std::vector<Read> &reads, int q, int n, size_t text_from)
 {
 	std::string want;
+	TallyInto nowhere(nullptr);                      // (a text made for comparison: not a record of the output)
 	for (int t = 0; t < n; ++t) sam_from_record(cx, reads[(size_t)(ck.begin + q + t)], ck.recs, ck.begin + q + t, want, ck.cigar_pool);
 	g_check_n += n;
 	if (want.size() == ck.text.size() - text_from && memcmp(want.data(), ck.text.data() + text_from, want.size()) == 0) return;

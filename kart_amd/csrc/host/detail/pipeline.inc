@@ -206,6 +206,7 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 			st.total_reads += ck.st.total_reads;
 			st.unmapped += ck.st.unmapped;
 			st.unique += ck.st.unique;
+			if (st.tally && ck.tally) *st.tally += *ck.tally;
 		}
 		est_latest.store(est_distance(cx, tot.iPaired, tot.iDistance));
 		if (shard.active() && shard.rank == 0) { shard.rdv->hint_paired.store(tot.iPaired); shard.rdv->hint_distance.store(tot.iDistance); }
@@ -277,6 +278,7 @@ void map_library(Ctx &cx, Source &src, FILE *out, Stats &st, RunTotals &tot, Sha
 			sb->set_tags(cx.opt.md);                    // (... and a run with -md one without)
 			sb->set_read_group(cx.opt.read_group_id(cx.lib));      // (... and a library with a read group one without, or with another)
 			sb->set_unmapped(cx.un());                  // (... and a run with -un one without)
+			sb->set_stats(cx.stats);                    // (... and a run with -stats one without)
 			sb->set_input(!cx.fastq);                   // (... and a FASTQ library a FASTA one)
 			Options &o = const_cast<Options &>(cx.opt);
 			const int64_t keep = o.batch_reads;

@@ -17,8 +17,18 @@ inline void append_int(std::string &out, long long v)   // what "%d" / "%lld" pr
 
 inline void append_qual(std::string &out, const Read &rd);
 
+// -stats: where the records this thread prints are tallied (null: nowhere) -- set around a chunk's stage C.  The three sites below that make a record's
+// text (sam_unmapped, sam_mapped_fields, sam_one_record's unmapped branch) are the only ones in the host pipeline, and each counts what it prints
+thread_local Tally *t_tally = nullptr;
+struct TallyInto {
+	Tally *prev;
+	explicit TallyInto(Tally *t) : prev(t_tally) { t_tally = t; }
+	~TallyInto() { t_tally = prev; }
+};
+
 void sam_unmapped(const Ctx &cx, const Read &rd, std::string &out)
 {
+	if (t_tally) t_tally->add(rd.rep[0].flag, 0, false, 0, std::string_view());
 	out += rd.name; out += '\t';
 	append_int(out, rd.rep[0].flag);
 	out += "\t*\t0\t0\t*\t*\t0\t0\t";
@@ -63,6 +73,7 @@ void sam_mapped_fields(const Ctx &cx, const Read &rd, int flag, int chr_idx, lon
                        long long mate_pos, int tlen, bool flip, int score, int sub_score, std::string &out)
 {
 	const std::string &chr = cx.ref.contigs[(size_t)chr_idx].name;
+	if (t_tally) t_tally->add(flag, mapq, has_mate, tlen, cigar);
 	size_t at = out.size();
 	out.resize(at + rd.name.size() + chr.size() + cigar.size() + rd.seq.size() + rd.qual.size() + 192 + (cx.opt.md ? md_room(cigar) : 0) + cx.rg_field.size());
 	char *p = &out[at];
@@ -102,6 +113,7 @@ void sam_mapped(const Ctx &cx, const Read &rd, const Report &rp, bool has_mate, 
 void sam_one_record(const Ctx &cx, const Read &rd, const kg_aln_record &rec, std::string &out, const char *cigar_pool = nullptr)
 {
 	if (rec.kind == KG_ALN_UNMAPPED) {
+		if (t_tally) t_tally->add(rec);
 		out += rd.name; out += '\t';
 		append_int(out, rec.flag);
 		out += "\t*\t0\t0\t*\t*\t0\t0\t";

@@ -642,6 +642,7 @@ void add_timing(kg_stream_timing_t &into, const kg_stream_timing_t &from)
 	into.text_checksum[0] += from.text_checksum[0]; into.text_checksum[1] += from.text_checksum[1];
 	for (int i = 0; i < 2; ++i) { into.un_kernel_ms[i] += from.un_kernel_ms[i]; into.un_kernel_launches[i] += from.un_kernel_launches[i]; }
 	into.un_bytes += from.un_bytes;
+	into.stats_kernel_ms += from.stats_kernel_ms; into.stats_kernel_launches += from.stats_kernel_launches; into.stats_bytes += from.stats_bytes;
 }
 
 // One library's run through the stream: K lane threads (lane_thread) feed the commit (the caller's thread) through `feed`.
@@ -838,12 +839,21 @@ struct StreamRun {
 			ck.recs = res.records;
 			ck.dev = res.chunk_stats[c];
 			ck.stream = true;
+			if (cx.stats) {
+				if (!res.chunk_tally) run_fail("the device stream returned no tally for a batch of a -stats run");
+				else ck.dev_tally = res.chunk_tally + (size_t)c * KG_STATS_WORDS;
+				ck.n_records_reads = res.n_reads; ck.n_records = res.n_records;
+			}
 			stream_list_host_reads(b, ck);
 			if (!ck.hq.empty()) busy.push_back(c);
 		}
 		// chunks without host reads need no work at all: their statistics are the device's (stage A's first lines)
 		for (ChunkState &ck : b.chunks)
-			if (ck.hq.empty()) { chunk_stage_a(cx, b.no_reads, res.cand_off, res.cands, res.cand_seeds, ck, b.est_dev); ck.text.clear(); ck.host_len.clear(); ck.st.total_reads = ck.count; }
+			if (ck.hq.empty()) {
+				chunk_stage_a(cx, b.no_reads, res.cand_off, res.cands, res.cand_seeds, ck, b.est_dev); ck.text.clear(); ck.host_len.clear(); ck.st.total_reads = ck.count;
+				// (-stats: no stage C for such a chunk -- its tally is the device's row)
+				if (cx.stats) { ck.tally = std::make_shared<Tally>(); chunk_device_tally(ck); }
+			}
 		// the others: their records and candidates come over now (the batch's result holds them only for the chunks asked for, kg_stream_fetch),
 		// then: plan on the pool, ONE gap-closing call for the batch's handed-back reads (a call per chunk was ~13 small device
 		// calls per 1 M-read batch behind one mutex), finish on the pool
@@ -946,6 +956,7 @@ struct StreamRun {
 			st.total_reads += ck.count;
 			st.unmapped += ck.st.unmapped;
 			st.unique += ck.st.unique;
+			if (st.tally && ck.tally) *st.tally += *ck.tally;
 			if (packer) packer->push(std::move(pieces), total, std::move(ck.text), &b.writes_pending, &b.res);
 			else writer->push_pieces(std::move(pieces), total, std::move(ck.text), &b.writes_pending, &feed.mu, &feed.cv);
 		}

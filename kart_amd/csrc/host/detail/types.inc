@@ -180,6 +180,7 @@ struct Ctx {
 	FILE *un_out[2] = {nullptr, nullptr};
 	class Writer *un_writer[2] = {nullptr, nullptr};
 	bool un() const { return un_out[0] != nullptr; }
+	bool stats = false;            // -stats: every chunk tallies the records it prints (ChunkState::tally)
 	std::string rg_field;          // -R: "\tRG:Z:<ID>" of the library being mapped, the last field of every record it prints; empty: none
 	const char *refseq() const { return ref.seq.get(); }
 };

@@ -86,6 +86,10 @@ public:
 	{
 		if (kg_stream_set_unmapped(s_, on ? 1 : 0) != KG_OK) die("kg_stream_set_unmapped");
 	}
+	void set_stats(bool on) override
+	{
+		if (kg_stream_set_stats(s_, on ? 1 : 0) != KG_OK) die("kg_stream_set_stats");
+	}
 	kg_stream *handle() const { return s_; }
 
 private:

@@ -201,6 +201,9 @@ int run_mapping(const Options &opt, const RefData &ref, KernelBackend &kern, FIL
 		if (!un_files.fp[f]) { fprintf(stderr, "Error! Cannot open file [%s]\n", name.c_str()); return 1; }
 	}
 	if (un_files.fp[0]) { cx.un_out[0] = un_files.fp[0]; cx.un_out[1] = un_files.fp[1]; }
+	// -stats: every chunk tallies the records it prints, the commit steps sum the chunks here in output order
+	if (!opt.stats.empty() && !stats.tally) stats.tally = std::make_shared<Tally>();
+	cx.stats = !opt.stats.empty();
 	Options &o = const_cast<Options &>(opt);
 	RunTotals tot;
 	// one process per GPU (shard.inc): this process maps shard_rank of shard_count chunk ranges of the library
@@ -356,6 +359,23 @@ std::string run_error_message()
 {
 	std::lock_guard<std::mutex> lk(g_run_err_mu);
 	return g_run_err;
+}
+
+bool open_stats(const Options &opt, FILE *&fp)
+{
+	fp = nullptr;
+	if (opt.stats.empty()) return true;
+	fp = fopen(opt.stats.c_str(), "w");
+	if (!fp) fprintf(stderr, "Error! Cannot open file [%s]\n", opt.stats.c_str());
+	return fp != nullptr;
+}
+
+bool write_stats(const Stats &st, FILE *fp)
+{
+	if (!fp) return true;
+	const std::string text = (st.tally ? *st.tally : Tally()).text();
+	const bool ok = fwrite(text.data(), 1, text.size(), fp) == text.size();
+	return fclose(fp) == 0 && ok;
 }
 
 FILE *open_output(const std::string &path)

@@ -16,6 +16,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <string_view>
 #include <utility>
 #include <vector>
 
@@ -45,6 +46,9 @@ struct Options {
 	// mates are: `samtools fastq -f 4` / `-f 12`), in input order, every library appended.  A two-file library (-f A -f2 B) takes both: records of A to
 	// un, of B to un2; parse_cli rejects anything else.  Empty: nothing is written
 	std::string un, un2;
+	// -stats FILE: a summary of the records the run printed (flags, MAPQ, insert sizes, CIGAR operations: detail/tally.inc), every library summed, written
+	// when the run is over; not with -shard or a device list.  Empty: nothing is counted
+	std::string stats;
 	bool fz_device = false;   // -fz device: the members of bgzip-ped read files are inflated on the device (default: host, zlib on the -t threads)
 	int device = 0;
 	std::vector<int> devices;       // -gpu a,b,c: one process per listed device, the input sharded between them
@@ -113,6 +117,8 @@ struct StreamBackend {
 	virtual void set_read_group(const std::string &id) { (void)id; }
 	// map() fills the result's un .. n_units from here on: the input text of the units whose reads are all unmapped (kg_stream_set_unmapped); while no lane works
 	virtual void set_unmapped(bool on) { (void)on; }
+	// map() fills the result's chunk_tally from here on: the tally of every chunk's records that the device decided (kg_stream_set_stats); while no lane works
+	virtual void set_stats(bool on) { (void)on; }
 };
 
 // The fragment pairs of one chunk whose alignment GenerateNormalPairAlignment (src/tools.cpp:142-223) is to produce -- 8-mer partition,
@@ -229,7 +235,11 @@ struct RefData {
 	bool load(const std::string &prefix, std::string &err, int threads = 16);
 };
 
+#include "detail/tally.inc"
+
 struct Stats {
+	// -stats: the tally of every record printed so far, in output order (null: nothing is counted)
+	std::shared_ptr<Tally> tally;
 	int64_t total_reads = 0, unmapped = 0, unique = 0, paired = 0, distance = 0;
 	double map_seconds = 0;     // first read in -> last SAM byte handed to the writer (index load excluded)
 	int64_t respeculated = 0;   // chunks re-mapped because their speculated EstDistance did not hold
@@ -255,6 +265,10 @@ int run_mapping(const Options &opt, const RefData &ref, KernelBackend &kern, FIL
 
 // the output file: read-write on a regular file (the writer places chunks through shared mappings), write-only otherwise (pipes)
 FILE *open_output(const std::string &path);
+// -stats: the summary file, opened (created, emptied) before anything is mapped so that a name that cannot be written fails the run at once; null without
+// the flag.  write_stats() puts the run's tally there and closes it; false: the name could not be opened / written
+bool open_stats(const Options &opt, FILE *&fp);
+bool write_stats(const Stats &st, FILE *fp);
 
 int parse_cli(int argc, char **argv, Options &opt);   // reference src/main.cpp:106-190; <0 = exit(code)
 

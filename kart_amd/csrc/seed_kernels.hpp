@@ -99,7 +99,8 @@ hipError_t launch_sample_sa(const uint32_t *fsa32, const uint64_t *fsa64, uint64
 enum { KT_CHAIN = 0, KT_ALN_PAIR, KT_ALN_RESCUE, KT_ALN_PLAN_FAST, KT_ALN_PLAN, KT_ALN_PARTITION, KT_NW, KT_ALN_FINISH, KT_ALN_FINAL,
        KT_SAM_SIZE, KT_SAM_FORMAT, KT_FQ_PARSE, KT_FQ_MATERIALISE, KT_LOCATE_SORT, KT_ALN_TRIVIAL, KT_BGZF,
        KT_UN_SIZE, KT_UN_COPY,         // kg_stream_set_unmapped (un_kernels.hip): kg_stream_timing_t::un_kernel_ms, behind the sixteen slots of kernel_ms
-       KT_SLOTS = 18 };
+       KT_STATS,                       // kg_stream_set_stats (stats_kernels.hip): kg_stream_timing_t::stats_kernel_ms
+       KT_SLOTS = 19 };
 // (a slot may be bracketed more than once per batch -- the NW kernels run for the batch and again for what comes back from the partition --: every
 //  bracket takes the slot's next pair of events, up to kKtRing of them between two reads of the timer; the reader sums the pairs used)
 constexpr int kKtRing = 4;
