@@ -810,7 +810,7 @@ int kgi_seed_resident(kg_workspace *ws, int mode, int min_seed_len, int occ_thr,
 
 // ONE seeding launch over the parsed batches of several stream lanes (abi_stream.hip): `ws` is the group's workspace, sized for
 // n_seg * stride read slots; ws->d_enc holds segment s's characters in its own part (the lanes materialise straight into it),
-// ws->d_read_off / group_read_len every slot's offset and length (stream_kernels.hip: group_publish_kernel), counts[s] the reads
+// ws->d_read_off / group_read_len every slot's offset and length (read_kernels.hip: group_publish_kernel), counts[s] the reads
 // segment s holds this round (0: the lane is absent).  The seeds of the whole group stay in ws->d_seeds / ws->d_seed_off;
 // seed_base[s] (s = 0 .. n_seg) = first seed of segment s, seed_base[n_seg] the total -- the lanes cut their slices out of that.
 int kgi_seed_group(kg_workspace *ws, int mode, int min_seed_len, int occ_thr, int n_seg, int64_t stride, const int64_t *counts, int64_t *seed_base)

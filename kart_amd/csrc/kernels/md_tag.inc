@@ -1,5 +1,5 @@
 // kernels/md_tag.inc -- the MD:Z field of a mapped record, computed where the record is sized and where it is printed (kg_stream_set_tags,
-// KG_STREAM_TAG_MD; the CLI's -md).  A fragment of stream_kernels.hip (included there, inside namespace kg { namespace { ... } }); not a translation unit.
+// KG_STREAM_TAG_MD; the CLI's -md).  A fragment of text_device.hpp (included there, inside namespace kg { namespace { ... } }, for sam_kernels.hip and bam_kernels.hip); not a translation unit.
 //
 // The reference prints no MD (its NM is rlen - score, no edit distance); every consumer of its output runs `samtools calmd` over the file next.  Here the
 // string is made from what the format kernels hold anyway: the 2-bit forward text, the read's characters and the record's contig, POS, strand and CIGAR.

@@ -1,4 +1,5 @@
-// stream_kernels.hpp -- argument blocks of the FASTQ/FASTA-text-in / SAM-text-out kernels (stream_kernels.hip) shared with the C ABI.
+// stream_kernels.hpp -- argument blocks and launchers of the FASTQ/FASTA-text-in / SAM-text-out kernels shared with the C ABI: the input side in
+// read_kernels.hip, the output side in sam_kernels.hip (which launches its own kernels or those of bam_kernels.hip).
 //
 // The reference parses its input one record at a time on the host (GetNextEntry / GetNextChunk, src/GetData.cpp:51-143) and prints
 // its output one record at a time (OutputPairedAlignments / OutputSingledAlignments, src/Mapping.cpp:177-315).  Here both ends run

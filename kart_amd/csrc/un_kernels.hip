@@ -2,20 +2,16 @@
 //
 //   un_size_kernel      one lane per unit (a read, or a pair): is it selected -- every read of it has the unmapped record with FLAG & 4; a pair the device
 //                       handed back (KG_ALN_HOST) is the caller's to decide -- and how many bytes its records take in either file -> scan -> offsets
-//   un_copy_kernel      one wave per 64 units and file: the selected spans as ONE list of 16-byte chunks, lane l taking chunks l, l + 64, ... (the form of
-//                       sam_format_kernel's phase 2b): consecutive lanes move consecutive chunks, whole memory lines per instruction on either side.  In an
+//   un_copy_kernel      one wave per 64 units and file: the selected spans as ONE list of 16-byte chunks, lane l taking chunks l, l + 64, ... (text_device.hpp,
+//                       as sam_format_kernel's phase 2b): consecutive lanes move consecutive chunks, whole memory lines per instruction on either side.  In an
 //                       ordinary run almost nothing is selected: a group whose offsets do not move leaves after two loads.
 // Byte work, HBM-bound: a selected byte is read once and written once.  Plain C++, vector loads and stores only.
 #include "un_kernels.hpp"
-
-#include <hipcub/hipcub.hpp>
+#include "text_device.hpp"
 
 namespace kg {
 
 namespace {
-
-// sixteen bytes at any address (one unaligned load / store)
-struct __attribute__((packed, aligned(1))) UnU128 { uint64_t lo, hi; };
 
 // where the records of unit u lie in file f: text[from, to), and whether the file's last line ends there without a line feed
 struct UnSpan {
@@ -44,21 +40,6 @@ __device__ __forceinline__ UnSpan unit_span(const UnArgs &a, int f, int64_t u)
 }
 
 __device__ __forceinline__ bool read_unmapped(const kg_aln_record &rec) { return rec.kind == KG_ALN_UNMAPPED && (rec.flag & 4) != 0; }
-
-__device__ __forceinline__ int wave_scan_inclusive(int v)
-{
-	const int lane = threadIdx.x & 63;
-	for (int d = 1; d < 64; d <<= 1) {
-		int t = __shfl_up(v, d);
-		if (lane >= d) v += t;
-	}
-	return v;
-}
-
-struct Widen32 {
-	__host__ __device__ __forceinline__ int64_t operator()(const int32_t &x) const { return (int64_t)x; }
-};
-using Wide32Iter = hipcub::TransformInputIterator<int64_t, Widen32, const int32_t *>;
 
 }  // namespace
 
@@ -128,29 +109,22 @@ __global__ __launch_bounds__(64) void un_copy_kernel(UnArgs a)
 				}
 			}
 			span_n[lane] = n;
-			const int incl = wave_scan_inclusive((n + 15) >> 4);
-			if (lane == 0) chunk_pre[0] = 0;
-			chunk_pre[lane + 1] = incl;
+			chunk_list(chunk_pre, lane, (n + 15) >> 4);
 		}
 		__syncthreads();
 		// ---- lane = chunk: sixteen bytes at a time, a span's last bytes one by one (the byte behind a span is another lane's) ---------------------
-		{
-			const int total = chunk_pre[64];
-			int unit = 0;
-			for (int idx = lane; idx < total; idx += 64) {
-				while (idx >= chunk_pre[unit + 1]) ++unit;
-				const int at = (idx - chunk_pre[unit]) << 4, n = span_n[unit];
-				const uint8_t *src = w.text + src_at[unit] + at;
-				uint8_t *dst = out + dst_at[unit] + at;
-				if (at + 16 <= n) {
-					*reinterpret_cast<UnU128 *>(dst) = *reinterpret_cast<const UnU128 *>(src);
-					moved += 16;
-				} else {
-					for (int k = 0; k < n - at; ++k) dst[k] = src[k];
-					moved += (unsigned long long)(n - at);
-				}
+		for_each_chunk(chunk_pre, lane, [&](int unit, int c) {
+			const int at = c << 4, n = span_n[unit];
+			const uint8_t *src = w.text + src_at[unit] + at;
+			uint8_t *dst = out + dst_at[unit] + at;
+			if (at + 16 <= n) {
+				*reinterpret_cast<U128 *>(dst) = *reinterpret_cast<const U128 *>(src);
+				moved += 16;
+			} else {
+				for (int k = 0; k < n - at; ++k) dst[k] = src[k];
+				moved += (unsigned long long)(n - at);
 			}
-		}
+		});
 		__syncthreads();
 	}
 	// the bytes this wave wrote: the caller holds the sum against the scan's total
@@ -162,19 +136,9 @@ hipError_t launch_un_size(const UnArgs &a, void *scan_temp, size_t scan_temp_byt
 {
 	kt_begin(KT_UN_SIZE, stream);
 	hipLaunchKernelGGL(un_reset_kernel, dim3(1), dim3(64), 0, stream, a);
-	if (a.n_units > 0) {
-		int64_t blocks = (a.n_units + 255) / 256;
-		if (blocks > (int64_t)n_cu * 16) blocks = (int64_t)n_cu * 16;
-		hipLaunchKernelGGL(un_size_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
-	}
+	if (a.n_units > 0) hipLaunchKernelGGL(un_size_kernel, dim3(grid_of(a.n_units, 256, n_cu * 16)), dim3(256), 0, stream, a);
 	for (int f = 0; f < (a.two_files ? 2 : 1); ++f) {
-		Wide32Iter it(a.un_len[f], Widen32());
-		size_t need = 0;
-		hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, it, a.un_off[f], (int)(a.n_units + 1), stream);
-		if (e != hipSuccess) return e;
-		if (need > scan_temp_bytes) return hipErrorInvalidValue;
-		size_t tb = scan_temp_bytes;
-		e = hipcub::DeviceScan::ExclusiveSum(scan_temp, tb, it, a.un_off[f], (int)(a.n_units + 1), stream);
+		const hipError_t e = scan_lengths(a.un_len[f], a.un_off[f], a.n_units + 1, scan_temp, scan_temp_bytes, stream);
 		if (e != hipSuccess) return e;
 	}
 	kt_end(KT_UN_SIZE, stream);
@@ -185,9 +149,7 @@ hipError_t launch_un_copy(const UnArgs &a, int n_cu, hipStream_t stream)
 {
 	if (a.n_units <= 0) return hipSuccess;
 	kt_begin(KT_UN_COPY, stream);
-	int64_t groups = (a.n_units + 63) / 64;
-	if (groups > (int64_t)n_cu * 32) groups = (int64_t)n_cu * 32;
-	hipLaunchKernelGGL(un_copy_kernel, dim3((unsigned)groups, a.two_files ? 2 : 1), dim3(64), 0, stream, a);
+	hipLaunchKernelGGL(un_copy_kernel, dim3(grid_of(a.n_units, 64, n_cu * 32), a.two_files ? 2 : 1), dim3(64), 0, stream, a);
 	kt_end(KT_UN_COPY, stream);
 	return hipGetLastError();
 }

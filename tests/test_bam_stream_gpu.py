@@ -1,4 +1,4 @@
-"""GPU: BAM records made on the device (kg_stream_set_format, bam_size_kernel / bam_format_kernel in kart_amd/csrc/stream_kernels.hip) against
+"""GPU: BAM records made on the device (kg_stream_set_format, bam_size_kernel / bam_format_kernel in kart_amd/csrc/bam_kernels.hip) against
 tests/bam_encode.py -- an encoder of the printed SAM line written from the SAM/BAM specification, which tests/test_bam_records_cpu.py holds the
 host's own encoder to -- and the product's -bo run through the device stream against the same run with the host's reader, printer and encoder."""
 import gzip

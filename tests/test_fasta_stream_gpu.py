@@ -1,5 +1,5 @@
 """GPU: FASTA read libraries through the device stream (kg_stream_set_input; fa_line / fa_head / fa_record / fa_materialise kernels in
-kart_amd/csrc/stream_kernels.hip) against the reference's readers restated in tests/fasta_reads.py, the output against the FASTQ form of the same
+kart_amd/csrc/read_kernels.hip) against the reference's readers restated in tests/fasta_reads.py, the output against the FASTQ form of the same
 reads with the quality column starred and against tests/bam_encode.py, and the product binary against the reference's golden SAM and against its
 own host path (KART_AMD_NO_STREAM=1 / KART_AMD_NO_GZ_STREAM=1)."""
 import gzip

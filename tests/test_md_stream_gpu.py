@@ -1,8 +1,8 @@
-"""GPU: MD:Z made on the device (kg_stream_set_tags; kernels/md_tag.inc in sam_size / sam_format / bam_size / bam_format of kart_amd/csrc/stream_kernels.hip)
+"""GPU: MD:Z made on the device (kg_stream_set_tags; kernels/md_tag.inc in sam_size / sam_format / bam_size / bam_format of kart_amd/csrc/sam_kernels.hip and bam_kernels.hip)
 against tests/md_plain.py -- the plain-Python MD of the printed SEQ, the CIGAR, POS and tests/golden/small.fa -- on a batch built for the kernel's edges:
 read lengths around the 32-base text words, starts at every phase of a word, contig ends, both strands and mates, mismatches in the first and last column
 and side by side, indels, clipped ends, characters that are no bases, and an MD longer than the 58 characters a lane keeps in the LDS (kMdLds in
-stream_kernels.hip: a longer one sends the read down the record-by-record path)."""
+text_device.hpp: a longer one sends the read down the record-by-record path)."""
 import re
 
 import numpy as np

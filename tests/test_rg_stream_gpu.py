@@ -1,5 +1,5 @@
 """GPU: the read group made on the device (kg_stream_set_read_group; the kRg instantiations of sam_size / sam_format / bam_size / bam_format in
-kart_amd/csrc/stream_kernels.hip).  The field is a constant of the batch, so the check needs no model: every line of a run with it is the line of the run
+kart_amd/csrc/sam_kernels.hip and bam_kernels.hip).  The field is a constant of the batch, so the check needs no model: every line of a run with it is the line of the run
 without it plus "\\tRG:Z:<ID>", on unmapped records, 1- and 2-base reads, chained records of multi_hit reads and records that take the record-by-record path
 alike; a BAM record is what the host's encoder makes of that line.  ID lengths sit on either side of the widths the copies use (16-byte pieces, 64 lanes)."""
 import gzip

@@ -1,4 +1,4 @@
-"""GPU: the device's FASTQ parser and SAM formatter (kg_stream_*, kart_amd/csrc/stream_kernels.hip) against the reference's own
+"""GPU: the device's FASTQ parser and SAM formatter (kg_stream_*, kart_amd/csrc/read_kernels.hip and sam_kernels.hip) against the reference's own
 arithmetic -- GetNextEntry / GetNextChunk (reference src/GetData.cpp:29-143) restated in a few lines of Python below -- and the
 product binary through that path against the golden SAM of the unmodified reference."""
 import gzip
